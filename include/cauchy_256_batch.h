@@ -46,7 +46,37 @@ int cauchy_256_decode_batch_out(int k, int m, int block_bytes, int groups, const
                                 const unsigned char *d_rows, void *d_out, unsigned char *d_out_rows,
                                 int *d_out_count, void *stream);
 
+/*
+ * Var-k batches: one launch for groups whose k differ (the caller closes a group with however
+ * many packets were queued; m and block_bytes move slowly). Groups are described CSR-style by one
+ * device array d_first[groups + 1]: group g owns blocks first[g] .. first[g+1]-1 of the packed
+ * arrays, so k_g = first[g+1] - first[g]; its blocks start at byte first[g] * block_bytes of d_data
+ * / d_blocks and its rows at byte first[g] of d_rows. Nothing is padded or aligned. total_blocks is
+ * the host's copy of first[groups]: it bounds every access, so no call reads d_first on the host
+ * and nothing synchronises.
+ *   recovery  [groups][m][block_bytes]; a recovery block of group g carries row k_g + y
+ *   out       [groups][emax][block_bytes], out_rows [groups][emax], emax = min(kmax, m)
+ * Per-group semantics and bytes are those of cauchy_256_encode(k_g, m, ..) / cauchy_256_decode(k_g,
+ * m, ..). The kernels are those cauchy_256_batch_path(kmax, m, block_bytes) reports, coding every
+ * k_g <= kmax (the generator's column x is the same for every k).
+ * Host-checked (-1, nothing enqueued): kmax in 2..255, kmax + m <= 256, block_bytes % 8 == 0,
+ * groups >= 0, 0 <= total_blocks <= groups * kmax, m >= 1 (encode) / m >= 2 (decode).
+ * Malformed groups -- k_g outside 2..kmax, or a span that leaves [0, total_blocks] -- are seen only
+ * by the device: nothing of them is read, encode writes all-zero recovery blocks, decode sets
+ * d_out_count[g] = -1, each is counted by cauchy_256_batch_errors(stream), and the other groups
+ * are coded as usual. (In a batch above 2 GiB whose malformed groups make first[] jump by more
+ * than 2 GiB inside one 128-column tile, the well-formed groups beyond the jump read as zeros.)
+ */
+int cauchy_256_encode_batch_var(int kmax, int m, int block_bytes, int groups, const int *d_first,
+                                int total_blocks, const void *d_data, void *d_recovery, void *stream);
+int cauchy_256_decode_batch_out_var(int kmax, int m, int block_bytes, int groups, const int *d_first,
+                                    int total_blocks, const void *d_blocks, const unsigned char *d_rows,
+                                    void *d_out, unsigned char *d_out_rows, int *d_out_count,
+                                    void *stream);
+
 /* Pre-allocate the internal decode workspace so later calls allocate nothing (graph capture).
+ * A reserve for (kmax, m, block_bytes, groups) is sufficient for a later
+ * cauchy_256_decode_batch_out_var with those parameters: it allocates nothing either.
  * Workspaces are per stream (decodes in flight on different streams never share scratch):
  * cauchy_256_batch_reserve sizes the null stream's workspace and the minimum size of every
  * workspace created later; cauchy_256_batch_reserve_stream does the same for `stream`. */
@@ -55,7 +85,9 @@ int cauchy_256_batch_reserve_stream(int k, int m, int block_bytes, int groups, v
 
 /* Malformed decode groups (more recovery blocks than erased originals: duplicate rows, outside
  * the reference's contract) are left untouched, counted, and flagged with d_out_count[g] = -1 by
- * cauchy_256_decode_batch_out. Counts are kept per stream: this waits for `stream` and returns the
+ * cauchy_256_decode_batch_out. The var-k calls count their malformed groups (k_g outside 2..kmax,
+ * a span outside [0, total_blocks]) in the same counter, encode and decode alike, on top of the
+ * decode's malformed rows. Counts are kept per stream: this waits for `stream` and returns the
  * number of such groups among the decodes enqueued on `stream` since the previous call for that
  * stream (read and reset in stream order), or -2 on a GPU error. The single-group
  * cauchy_256_decode returns -1 for such a group and counts it nowhere (it decodes on a private

@@ -18,8 +18,11 @@
  * These entry points do the same for many groups per call: framing on host threads into pinned
  * staging, groups bucketed by (k, m, block_bytes), one batched GPU launch per bucket chunk
  * (cauchy_256_encode_batch / cauchy_256_decode_batch_out), chunks double-buffered so host
- * framing overlaps the PCIe copies and the kernels. The bytes on the wire are exactly the
- * reference's. Host buffers only; any alignment.
+ * framing overlaps the PCIe copies and the kernels. Groups whose k differ but which the codec
+ * would code with the same compiled kernel (a compiled K >= k of the same m, cauchy_256_batch_path
+ * = 1) share one bucket keyed by (K, m, block_bytes) and one var-k launch
+ * (cauchy_256_encode_batch_var / cauchy_256_decode_batch_out_var). The bytes on the wire are
+ * exactly the reference's. Host buffers only; any alignment.
  *
  * Return codes: >= 0 ok (see each call), -1 invalid arguments, -2 GPU/runtime error.
  */
@@ -74,6 +77,11 @@ typedef void (*shorthair_on_packet_fn)(void *ctx, int group, int id, const unsig
  * (measurement), nothing delivered. */
 int shorthair_recover_groups(const ShorthairRxGroup *groups, int count, shorthair_on_packet_fn on_packet,
                              void *ctx);
+
+/* Process-wide cumulative counts since the library was loaded: batched codec launches issued by
+ * the two calls above (one per bucket chunk) and groups coded by them. Either pointer may be NULL.
+ * Returns 0. */
+int shorthair_groups_stats(long long *launches, long long *groups);
 
 #ifdef __cplusplus
 }

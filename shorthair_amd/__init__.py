@@ -14,6 +14,7 @@ import os
 
 __all__ = ["lib", "Block", "CAUCHY_256_VERSION", "cauchy_256_init", "cauchy_256_encode",
            "cauchy_256_decode", "encode_batch", "decode_batch", "decode_batch_out",
+           "encode_batch_var", "decode_batch_out_var", "groups_stats",
            "fill_synthetic", "erasure_pattern", "batch_reserve", "batch_errors", "has_fixed", "path", "default_stream", "sync", "LIB_PATH",
            "EXPORTED_SYMBOLS"]
 
@@ -25,13 +26,15 @@ LIB_PATH = os.environ.get("SH_LIB_PATH") or os.path.join(os.path.dirname(os.path
 EXPORTED_SYMBOLS = [
     "_cauchy_256_init", "cauchy_256_encode", "cauchy_256_decode",
     "cauchy_256_batch_init", "cauchy_256_encode_batch", "cauchy_256_decode_batch",
-    "cauchy_256_decode_batch_out", "cauchy_256_batch_reserve", "cauchy_256_batch_reserve_stream",
+    "cauchy_256_decode_batch_out", "cauchy_256_encode_batch_var", "cauchy_256_decode_batch_out_var",
+    "cauchy_256_batch_reserve", "cauchy_256_batch_reserve_stream",
     "cauchy_256_batch_errors", "cauchy_256_batch_path", "cauchy_256_fill_synthetic",
     "cauchy_256_erasure_pattern",
     "cauchy_256_default_stream", "cauchy_256_sync", "cauchy_256_profile", "cauchy_256_profile_read",
     "gf256_init_", "gf256_add_mem", "gf256_add2_mem", "gf256_addset_mem", "gf256_mul_mem",
     "gf256_muladd_mem", "gf256_memswap",
     "shorthair_recovery_packet_bytes", "shorthair_encode_groups", "shorthair_recover_groups",
+    "shorthair_groups_stats",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -70,6 +73,12 @@ lib.cauchy_256_decode_batch.argtypes = [_c.c_int] * 4 + [_c.c_void_p] * 3
 lib.cauchy_256_decode_batch.restype = _c.c_int
 lib.cauchy_256_decode_batch_out.argtypes = [_c.c_int] * 4 + [_c.c_void_p] * 6
 lib.cauchy_256_decode_batch_out.restype = _c.c_int
+lib.cauchy_256_encode_batch_var.argtypes = [_c.c_int] * 4 + [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 3
+lib.cauchy_256_encode_batch_var.restype = _c.c_int
+lib.cauchy_256_decode_batch_out_var.argtypes = [_c.c_int] * 4 + [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 6
+lib.cauchy_256_decode_batch_out_var.restype = _c.c_int
+lib.shorthair_groups_stats.argtypes = [_c.c_void_p, _c.c_void_p]
+lib.shorthair_groups_stats.restype = _c.c_int
 lib.cauchy_256_batch_reserve.argtypes = [_c.c_int] * 4
 lib.cauchy_256_batch_reserve.restype = _c.c_int
 lib.cauchy_256_batch_reserve_stream.argtypes = [_c.c_int] * 4 + [_c.c_void_p]
@@ -152,6 +161,31 @@ def decode_batch_out(k, m, block_bytes, groups, blocks, rows, out, out_rows, out
     return _check(lib.cauchy_256_decode_batch_out(k, m, block_bytes, groups, _ptr(blocks), _ptr(rows),
                                                   _ptr(out), _ptr(out_rows), _ptr(out_count),
                                                   _stream(stream)), "decode_batch_out")
+
+
+def encode_batch_var(kmax, m, block_bytes, groups, first, total_blocks, data, recovery, stream=None):
+    """Var-k encode: first int32 cuda tensor [groups + 1] (group g = blocks first[g]..first[g+1]-1),
+    data uint8 [total_blocks][B] packed, recovery [groups][m][B]."""
+    return _check(lib.cauchy_256_encode_batch_var(kmax, m, block_bytes, groups, _ptr(first), total_blocks,
+                                                  _ptr(data), _ptr(recovery), _stream(stream)),
+                  "encode_batch_var")
+
+
+def decode_batch_out_var(kmax, m, block_bytes, groups, first, total_blocks, blocks, rows, out, out_rows,
+                         out_count, stream=None):
+    """Var-k out-of-place decode: blocks [total_blocks][B] and rows [total_blocks] packed by `first`;
+    out [groups][min(kmax,m)][B], out_rows [groups][min(kmax,m)], out_count int32 [groups]."""
+    return _check(lib.cauchy_256_decode_batch_out_var(kmax, m, block_bytes, groups, _ptr(first), total_blocks,
+                                                      _ptr(blocks), _ptr(rows), _ptr(out), _ptr(out_rows),
+                                                      _ptr(out_count), _stream(stream)),
+                  "decode_batch_out_var")
+
+
+def groups_stats():
+    """(launches, groups): cumulative batched codec launches and groups coded by the packet-group layer."""
+    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    lib.shorthair_groups_stats(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
 
 
 def fill_synthetic(out, n, block_bytes, groups, g0, cfg, stream=None):

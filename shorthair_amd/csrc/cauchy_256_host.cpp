@@ -418,12 +418,20 @@ const std::vector<TileLaunch> *tile_plan(Context &c, int k, int m, bool dec) {
 // Batched calls take the caller's stream verbatim (NULL = the null stream, as in HIP itself).
 hipStream_t pick(void *stream) { return static_cast<hipStream_t>(stream); }
 
+// A var-k batch (cauchy_256_*_var): group g owns blocks first[g] .. first[g + 1] - 1 of a packed
+// array of `total` blocks; `first` is device memory and is never read on the host.
+struct VarSpec {
+    const int *first = nullptr;
+    int total = 0;
+};
+
 // One launch of a compile-time-scheduled kernel over the whole batch (the kernels build their
 // buffer descriptors per workgroup, so 32-bit offsets never limit the batch size).
 // split: the stream's split-tile scratch (nullptr: whole tiles only).
 hipError_t launch_fixed_batch(int k, int m, int B, int groups, const uint8_t *in, long long in_gs,
                               uint8_t *out, long long out_gs, const uint8_t *pos,
-                              const uint8_t *rpos, bool dec, hipStream_t s, const SplitLease *split = nullptr) {
+                              const uint8_t *rpos, bool dec, hipStream_t s, const SplitLease *split = nullptr,
+                              const VarSpec *var = nullptr) {
     sh::FixedArgs a{};
     if (split) {
         a.split_part = split->part;
@@ -441,6 +449,11 @@ hipError_t launch_fixed_batch(int k, int m, int B, int groups, const uint8_t *in
     a.geo = sh::fixed_geometry(B);
     a.pos = pos;
     a.rpos = rpos;
+    if (var) {  // k = kmax; the input is the packed block array
+        a.first = var->first;
+        a.total_blocks = var->total;
+        a.in_bytes = static_cast<long long>(var->total) * B;
+    }
     return sh::launch_fixed(k, m, a, dec, s);
 }
 
@@ -462,7 +475,7 @@ int latency_slices(int nsteps) {
 // the steps are then sliced and the partials XOR-reduced into `out`.
 int launch_tile_batch(Context &c, int k, int m, int B, int groups, const uint8_t *in, long long in_gs,
                       uint8_t *out, long long out_gs, const uint8_t *pos, const uint8_t *rpos, bool dec,
-                      hipStream_t s, uint8_t *slice_scratch = nullptr) {
+                      hipStream_t s, uint8_t *slice_scratch = nullptr, const VarSpec *var = nullptr) {
     const std::vector<TileLaunch> *plan = tile_plan(c, k, m, dec);
     if (!plan) return -2;
     for (const TileLaunch &L : *plan) {
@@ -480,6 +493,11 @@ int launch_tile_batch(Context &c, int k, int m, int B, int groups, const uint8_t
         t.f.geo = sh::fixed_geometry(B);
         t.f.pos = pos;
         t.f.rpos = rpos;
+        if (var) {  // k = kmax; the input is the packed block array
+            t.f.first = var->first;
+            t.f.total_blocks = var->total;
+            t.f.in_bytes = static_cast<long long>(var->total) * B;
+        }
         t.targets = L.targets;
         t.tstride = L.tstride;
         t.snip_hi = L.hi;
@@ -561,6 +579,57 @@ int encode_batch(int k, int m, int B, int groups, const uint8_t *d_in, uint8_t *
     a.rowbytes = c.d_rowbytes;
     a.groups = groups;
     a.geo = sh::make_geometry(B);
+    SH_CHECK(sh::launch_apply(a, false, s));
+    return 0;
+}
+
+// Var-k encode (cauchy_256_encode_batch_var; parameters already checked): the kernels of
+// cauchy_256_batch_path(kmax, m, B) in their var-k form, one launch for every k_g <= kmax, and a
+// small launch that counts the malformed groups into the stream's error counter.
+int encode_batch_var(int kmax, int m, int B, int groups, const VarSpec &var, const uint8_t *d_in, uint8_t *d_out,
+                     hipStream_t s) {
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    if (groups <= 0) return 0;
+    StreamState *st = stream_state(c, s);
+    if (!st) return -2;
+    const long long out_gs = static_cast<long long>(m) * B;
+    {
+        // under the stream's lock, like a decode's count: cauchy_256_batch_errors reads and clears
+        // the counter either before this call's count or after it
+        std::lock_guard<std::mutex> g(st->mu);
+        SH_CHECK(sh::launch_var_check(var.first, var.total, kmax, groups, st->d_errors, s));
+    }
+    if (m == 1) {
+        SH_CHECK(sh::launch_xor_rows_var(d_in, var.first, var.total, kmax, d_out, out_gs, B, groups, s));
+        return 0;
+    }
+    if (sh::has_fixed(kmax, m, B) && !force_tile()) {
+        SH_CHECK(launch_fixed_batch(kmax, m, B, groups, d_in, 0, d_out, out_gs, nullptr, nullptr, false, s, nullptr,
+                                    &var));
+        return 0;
+    }
+    if (tile_usable(c, kmax, m, B))
+        return launch_tile_batch(c, kmax, m, B, groups, d_in, 0, d_out, out_gs, nullptr, nullptr, false, s, nullptr,
+                                 &var);
+    uint8_t *gen = generator(c, kmax, m);
+    if (!gen) return -2;
+    sh::ApplyArgs a{};
+    a.in = d_in;
+    a.in_bstride = B;
+    a.n_in = kmax;
+    a.out = d_out;
+    a.out_gstride = out_gs;
+    a.out_bstride = B;
+    a.n_out = m;
+    a.coef = gen;  // column x of the (kmax, m) generator is column x of every (k <= kmax, m)
+    a.coef_ld = round4(kmax);
+    a.rowbytes = c.d_rowbytes;
+    a.groups = groups;
+    a.geo = sh::make_geometry(B);
+    a.first = var.first;
+    a.total_blocks = var.total;
     SH_CHECK(sh::launch_apply(a, false, s));
     return 0;
 }
@@ -726,7 +795,7 @@ hipError_t launch_stage_b(const DecodeWS &w, int n_in, int B, int groups, uint8_
 // host_decode_setup below) and arrive with the blocks: no setup kernel.
 int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_blocks,
                 const uint8_t *d_rows, DecodeWS &w, int *errors, uint8_t *dst, hipStream_t s,
-                uint8_t *slice_scratch = nullptr, bool host_setup = false) {
+                uint8_t *slice_scratch = nullptr, bool host_setup = false, const VarSpec *var = nullptr) {
     uint8_t *gen = generator(c, k, m);
     if (!gen) return -2;
     sh::DecodeSetupArgs sa{};
@@ -757,6 +826,10 @@ int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_bl
     sa.targets = w.targets;
     sa.snip_base = c.snip_base;
     sa.errors = errors;
+    if (var) {  // k = kmax: the generator rows and X' are kmax wide, every group has its own k_g
+        sa.first = var->first;
+        sa.total_blocks = var->total;
+    }
     hipEvent_t *ev = nullptr;
     {  // check and claim the slot in one critical section (profile() may resize the ring)
         std::lock_guard<std::mutex> g(c.mu);
@@ -785,15 +858,15 @@ int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_bl
                             w.kp == round4(k);
         if (sh::has_fixed(k, m, B) && !force_tile() && !sliced) {
             SplitLease sp;
-            const bool split = kSplitLaunch && groups >= kSplitMinGroups;
+            const bool split = kSplitLaunch && groups >= kSplitMinGroups && !var;
             if (split)
                 if (int rc = lease_split(c, s, sp)) return rc;
             SH_CHECK(launch_fixed_batch(k, m, B, groups, d_blocks, static_cast<long long>(k) * B,
                                         w.residual, static_cast<long long>(m) * B, w.pos, w.rpos, true, s,
-                                        split ? &sp : nullptr));
+                                        split ? &sp : nullptr, var));
         } else if (int rc = launch_tile_batch(c, k, m, B, groups, d_blocks, static_cast<long long>(k) * B,
                                               w.residual, static_cast<long long>(m) * B, w.pos, w.rpos, true, s,
-                                              sliced ? slice_scratch : nullptr)) {
+                                              sliced ? slice_scratch : nullptr, var)) {
             return rc;
         }
         if (ev) SH_CHECK(hipEventRecord(ev[2], s));
@@ -819,6 +892,10 @@ int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_bl
     a.rowbytes = c.d_rowbytes;
     a.groups = groups;
     a.geo = geo;
+    if (var) {
+        a.first = var->first;
+        a.total_blocks = var->total;
+    }
     SH_CHECK(sh::launch_apply(a, true, s));
     // Stage B: recovered_j = sum_i M(S^-1[j][i]) residual_i
     SH_CHECK(launch_stage_b(w, w.emax, B, groups, dst, s));
@@ -987,6 +1064,49 @@ extern "C" int cauchy_256_decode_batch_out(int k, int m, int block_bytes, int gr
                        ls.errors, static_cast<uint8_t *>(d_out), s);
 }
 
+namespace {
+// Host-checked parameters of the var-k calls (cauchy_256_batch.h): false = -1, nothing enqueued.
+bool var_params_ok(int kmax, int m, int mmin, int B, int groups, int total_blocks) {
+    return kmax >= 2 && kmax <= 255 && m >= mmin && kmax + m <= 256 && B > 0 && B % 8 == 0 && groups >= 0 &&
+           total_blocks >= 0 && static_cast<long long>(total_blocks) <= static_cast<long long>(groups) * kmax;
+}
+}  // namespace
+
+extern "C" int cauchy_256_encode_batch_var(int kmax, int m, int block_bytes, int groups, const int *d_first,
+                                           int total_blocks, const void *d_data, void *d_recovery,
+                                           void *stream) {
+    if (!var_params_ok(kmax, m, 1, block_bytes, groups, total_blocks)) return -1;
+    VarSpec var;
+    var.first = d_first;
+    var.total = total_blocks;
+    return encode_batch_var(kmax, m, block_bytes, groups, var, static_cast<const uint8_t *>(d_data),
+                            static_cast<uint8_t *>(d_recovery), pick(stream));
+}
+
+extern "C" int cauchy_256_decode_batch_out_var(int kmax, int m, int block_bytes, int groups, const int *d_first,
+                                               int total_blocks, const void *d_blocks,
+                                               const unsigned char *d_rows, void *d_out,
+                                               unsigned char *d_out_rows, int *d_out_count, void *stream) {
+    if (!var_params_ok(kmax, m, 2, block_bytes, groups, total_blocks)) return -1;
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    if (groups <= 0) return 0;
+    hipStream_t s = pick(stream);
+    VarSpec var;
+    var.first = d_first;
+    var.total = total_blocks;
+    // the workspace of the uniform (kmax, m) decode: cauchy_256_batch_reserve(kmax, ...) covers it
+    DecodeWS w{};
+    WsLease ls;
+    if (int rc = lease_workspace(c, s, carve(w, nullptr, kmax, m, block_bytes, groups, false), ls)) return rc;
+    carve(w, ls.p, kmax, m, block_bytes, groups, false);
+    w.erasures = d_out_rows;
+    w.e = d_out_count;
+    return decode_core(c, kmax, m, block_bytes, groups, static_cast<const uint8_t *>(d_blocks), d_rows, w,
+                       ls.errors, static_cast<uint8_t *>(d_out), s, nullptr, false, &var);
+}
+
 extern "C" int cauchy_256_batch_reserve(int k, int m, int block_bytes, int groups) {
     return cauchy_256_batch_reserve_stream(k, m, block_bytes, groups, nullptr);
 }
@@ -999,6 +1119,10 @@ extern "C" int cauchy_256_batch_reserve_stream(int k, int m, int block_bytes, in
     DecodeWS w{};
     const size_t need = carve(w, nullptr, k, m, block_bytes, groups, true);
     if (!generator(c, k, m)) return -2;
+    // the tile kernels' snippet-address tables of this shape, so a later decode allocates nothing
+    if (block_bytes % 8 == 0 && (!sh::has_fixed(k, m, block_bytes) || force_tile()) &&
+        tile_usable(c, k, m, block_bytes) && !tile_plan(c, k, m, true))
+        return -2;
     size_t cur = c.ws_reserve.load();
     while (cur < need && !c.ws_reserve.compare_exchange_weak(cur, need)) {
     }

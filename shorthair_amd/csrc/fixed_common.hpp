@@ -173,12 +173,45 @@ __device__ __forceinline__ WGInfo tile_info(int nq, long long col0, long long lo
     return w;
 }
 
-template <class S, bool DEC>
+// Var-k batches (FixedArgs::first): the window of a tile's input. The tile's groups are packed
+// blocks first[g] .. first[g + 1] - 1, so its buffer descriptor starts at the lowest first block
+// among the tile's well-formed groups (the same value in every lane of the workgroup) and the chunk
+// offsets are relative to it. INT_MAX: the tile has no well-formed group.
+__device__ __forceinline__ int var_window(const FixedArgs &a, int g_first, int kmax) {
+    int lo = 0x7FFFFFFF;
+    for (int i = threadIdx.x & 63; i < a.groups_per_wg; i += 64) {
+        int f, k;
+        if (g_first + i < a.groups && var_group(a.first, g_first + i, kmax, a.total_blocks, f, k)) lo = min(lo, f);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) lo = min(lo, __shfl_xor(lo, d));
+    return __builtin_amdgcn_readfirstlane(lo);
+}
+
+// Var-k batches: offset of group gx's first block from the window f0 (OOR: malformed, outside the
+// workgroup's columns (`in` false), or ending past the descriptor's 2 GiB) and its k (0 then).
+__device__ __forceinline__ uint32_t var_base(const FixedArgs &a, int gx, bool in, int kmax, int f0, int &kg) {
+    int f = 0;
+    kg = 0;
+    if (!in || !var_group(a.first, gx, kmax, a.total_blocks, f, kg)) return OOR;
+    const long long rel = (static_cast<long long>(f) - f0) * a.geo.B;
+    if (rel < 0 || rel + static_cast<long long>(kg) * a.geo.B > 0x7FFFFFFFll) {
+        kg = 0;
+        return OOR;
+    }
+    return static_cast<uint32_t>(rel);
+}
+
+// VAR: the var-k source form (FixedArgs::first). A chunk's group base is (first[g] - window) * B
+// instead of gl * in_gstride, and encode's zero-step test is per chunk (the k of its group);
+// malformed groups read nothing. Everything else, and the whole VAR = false form, is unchanged.
+template <class S, bool DEC, bool VAR = false>
 struct Src {
     static constexpr bool kStream = false, kBlk = false;
     __amdgpu_buffer_rsrc_t rsrc;
     uint32_t dbase[S::DPW];   // chunk source offset, block 0 / array slot 0 (OOR past the batch)
     int dgl[S::DPW];          // decode: the chunk's group (position-table index)
+    int kc[S::DPW];           // VAR encode: k of the chunk's group (its steps x >= kc read zeros)
     uint32_t B, sub;
     int wave;
     uint32_t rd;              // this lane's read offset in a slot (c * 4)
@@ -227,17 +260,43 @@ struct Src {
         }
     }
 
+    __device__ __forceinline__ void init_var(const FixedArgs &a, const WGInfo &w) {
+        const Geometry &geo = a.geo;
+        const int kmax = a.k_rt > 0 ? a.k_rt : S::K;
+        int f0 = var_window(a, w.g_first, kmax);
+        if (f0 == 0x7FFFFFFF) f0 = 0;  // no well-formed group: every chunk below is OOR
+        const long long start = static_cast<long long>(f0) * geo.B;
+        long long n = a.in_bytes - start;
+        n = n < 0 ? 0 : (n > 0x7FFFFFFFll ? 0x7FFFFFFFll : n);
+        rsrc = make_rsrc(a.in + start, static_cast<uint32_t>(n));
+#pragma unroll
+        for (int j = 0; j < S::DPW; ++j) {
+            const int off = (w.wave * S::DPW + j) * 64 * S::W + w.lane * S::W;
+            const int aa = off / S::ROWB;
+            const int cc = (off - aa * S::ROWB) / 4;
+            const long long colx = w.col0 + cc;
+            const int gx = colx >= 0 ? static_cast<int>(colx / geo.nq) : -1;
+            const int qx = static_cast<int>(colx - static_cast<long long>(gx) * geo.nq);
+            dgl[j] = gx - w.g_first;
+            const uint32_t gb = var_base(a, gx, colx >= w.lo && colx < w.hi, kmax, f0, kc[j]);
+            dbase[j] = gb == OOR ? OOR : gb + col_off(qx, geo) + aa * geo.sub;
+        }
+        int kl;
+        const uint32_t lb = var_base(a, w.g_first + w.gl, w.valid, kmax, f0, kl);
+        lbase = lb == OOR ? OOR : lb + col_off(w.q, geo);
+    }
+
     __device__ __forceinline__ void init(const FixedArgs &a, const WGInfo &w, const uint8_t *lds_ring,
                                          const uint8_t *lds_pos) {
         const Geometry &geo = a.geo;
-        rsrc = wg_rsrc(a.in, a.in_bytes, a.in_gstride, w.g_first);
+        if constexpr (!VAR) rsrc = wg_rsrc(a.in, a.in_bytes, a.in_gstride, w.g_first);
         B = geo.B;
         sub = geo.sub;
         lds = lds_ring;
         pos = lds_pos;
         wave = w.wave;
         rd = static_cast<uint32_t>(w.c) * 4u;
-        chunk_src(a.geo, a.in_gstride, w, dbase, dgl);
+        if constexpr (!VAR) chunk_src(a.geo, a.in_gstride, w, dbase, dgl);
         in_ptr = a.in;
         nq = geo.nq;
         groups = a.groups;
@@ -246,7 +305,10 @@ struct Src {
         lgl = w.gl;
         pf_stride = a.pf_stride;
         krt = a.k_rt > 0 ? a.k_rt : S::K;
-        lbase = w.valid ? static_cast<uint32_t>(w.gl) * static_cast<uint32_t>(a.in_gstride) + col_off(w.q, geo) : OOR;
+        if constexpr (VAR)
+            init_var(a, w);
+        else
+            lbase = w.valid ? static_cast<uint32_t>(w.gl) * static_cast<uint32_t>(a.in_gstride) + col_off(w.q, geo) : OOR;
     }
 
     // Decode, generator switch SH_RINIT=1 (not the default: same time, more fetched bytes):
@@ -312,6 +374,7 @@ struct Src {
     }
 
     __device__ __forceinline__ void prefetch_next(int np) const {
+        static_assert(!VAR, "persistent tiles assume the uniform group stride");
         if (!has_next) return;
         auto *self = const_cast<Src *>(this);
         {  // the next tile's source, computed here: nothing of it is live across the body
@@ -360,6 +423,7 @@ struct Src {
     };
     template <int N>
     __device__ __forceinline__ L2Pf<N> l2_prefetch() const {
+        static_assert(!VAR, "the L2 prefetch assumes the uniform group stride");
         L2Pf<N> pf;
 #pragma unroll
         for (int i = 0; i < N * S::DPW; ++i) pf.v[i] = 0;
@@ -455,7 +519,7 @@ struct Src {
                 const uint32_t o = (p == 0xFF || dbase[j] == OOR) ? OOR : dbase[j] + static_cast<uint32_t>(p) * B;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, S::W, o, 0, 0, SH_LOAD_AUX);
             } else {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, S::W, x + x0s < krt ? dbase[j] : OOR,
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, S::W, x + x0s < (VAR ? kc[j] : krt) ? dbase[j] : OOR,
                                                          static_cast<uint32_t>(x) * B + boff, 0, SH_LOAD_AUX);
             }
         }
@@ -1089,12 +1153,15 @@ inline int split_count(const FixedArgs &a, int ntiles, void (*kern)(FixedArgs), 
     return n >= 8 ? static_cast<int>(n) : 0;
 }
 
-template <class S, bool DEC, bool STREAM = false, bool PERS = false, bool SPLIT = false>
+template <class S, bool DEC, bool STREAM = false, bool PERS = false, bool SPLIT = false, bool VAR = false>
 inline hipError_t launch_shape(FixedArgs a, hipStream_t s, void (*kern)(FixedArgs), const char *tag = nullptr,
                                int ntiles = -1) {
     constexpr bool dec = DEC;
-    // a runtime k below K: only the product source (Src) reads zeros past k
-    if (a.k_rt > 0 && a.k_rt != S::K && (STREAM || S::SLOT != S::IMG)) return hipErrorNotSupported;
+    // a runtime k below K, or per-group k: only the product source (Src) of a one-tile workgroup
+    // reads zeros past k (the persistent form sets up its next tile with the compile-time K)
+    constexpr bool product_src = !(STREAM || S::SLOT != S::IMG || PERS);
+    if (a.k_rt > 0 && a.k_rt != S::K && !product_src) return hipErrorNotSupported;
+    if ((VAR || a.first) && !(VAR && a.first && product_src)) return hipErrorNotSupported;
     a.groups_per_wg = (S::COLS - 1) / a.geo.nq + 2;
     // ring (the row images of the epilogue alias it); a streaming source needs only the images
     constexpr size_t front = STREAM ? 2ull * S::PW * S::SLOT : static_cast<size_t>(S::R) * S::SLOT;
@@ -1197,6 +1264,33 @@ __device__ __forceinline__ long long tile_col0(int tile, int cols_per_tile) {
         const long long cols_ = static_cast<long long>(a.groups) * a.geo.nq;                      \
         return launch_shape<Shape_##NAME##_##MODE, DEC, STREAM, false, (SPLIT) != 0>(             \
             a, s, kern_##NAME##_##MODE, #NAME "_" #MODE, tiles_of<Shape_##NAME##_##MODE, BLKSUB>(cols_)); \
+    }                                                                                             \
+    }                                                                                             \
+    }
+
+// The var-k form of a generated (k, m) (FixedArgs::first, Src<S, DEC, true>): the same generated
+// program over the per-group source, one tile per workgroup, as kern_<name>_<mode>v.
+#define FIXED_KERNEL_VAR(NAME, K, M, P, CW, R, MINW, MODE, DEC)                                   \
+    namespace sh {                                                                                \
+    namespace fixed {                                                                             \
+    using Shape_##NAME##_##MODE##v = Shape<K, M, P, CW, R>;                                       \
+    __global__ __launch_bounds__(64 * CW * P, MINW) void kern_##NAME##_##MODE##v(FixedArgs a) {   \
+        extern __shared__ __attribute__((aligned(16))) uint8_t lds[];                             \
+        using S = Shape_##NAME##_##MODE##v;                                                       \
+        Src<S, DEC, true> src;                                                                    \
+        RowSink<S> sink;                                                                          \
+        const long long cols_ = static_cast<long long>(a.groups) * a.geo.nq;                      \
+        const int ntiles_ = tiles_of<S, 0>(cols_);                                                \
+        int hgrp = 0;                                                                             \
+        const int tile = tile_of<S>(a, hgrp, ntiles_);                                            \
+        const long long c0 = tile_col0<0>(tile, S::COLS);                                         \
+        const int part = kernel_prologue<S, DEC>(a, lds, src, sink, c0, 0, cols_, 0, hgrp);        \
+        run_##NAME##_##MODE(part, src, sink);                                                     \
+    }                                                                                             \
+    hipError_t launch_##NAME##_##MODE##v(FixedArgs a, hipStream_t s) {                            \
+        const long long cols_ = static_cast<long long>(a.groups) * a.geo.nq;                      \
+        return launch_shape<Shape_##NAME##_##MODE##v, DEC, false, false, false, true>(            \
+            a, s, kern_##NAME##_##MODE##v, nullptr, tiles_of<Shape_##NAME##_##MODE##v, 0>(cols_)); \
     }                                                                                             \
     }                                                                                             \
     }

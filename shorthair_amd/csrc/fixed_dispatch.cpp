@@ -15,7 +15,9 @@ namespace sh {
 namespace fixed {
 #define SH_DECL(K, M)                                                    \
     hipError_t launch_k##K##_m##M##_enc(FixedArgs a, hipStream_t s);     \
-    hipError_t launch_k##K##_m##M##_dec(FixedArgs a, hipStream_t s);
+    hipError_t launch_k##K##_m##M##_dec(FixedArgs a, hipStream_t s);     \
+    hipError_t launch_k##K##_m##M##_encv(FixedArgs a, hipStream_t s);    \
+    hipError_t launch_k##K##_m##M##_decv(FixedArgs a, hipStream_t s);
 SH_FIXED_CONFIGS(SH_DECL)
 #undef SH_DECL
 
@@ -96,6 +98,12 @@ hipError_t launch_fixed(int k, int m, FixedArgs a, bool dec, hipStream_t stream)
     if (kk == 0) return hipErrorNotSupported;
     if (a.groups <= 0) return hipSuccess;
     a.k_rt = k;
+    // var-k batches (a.first): k is the largest group's, the kernels are the var instantiations
+#define SH_GO(K, M)                                                                         \
+    if (a.first && kk == K && m == M)                                                       \
+        return dec ? fixed::launch_k##K##_m##M##_decv(a, stream) : fixed::launch_k##K##_m##M##_encv(a, stream);
+    SH_FIXED_CONFIGS(SH_GO)
+#undef SH_GO
 #define SH_GO(K, M)                                                                         \
     if (kk == K && m == M)                                                                  \
         return dec ? fixed::launch_k##K##_m##M##_dec(a, stream) : fixed::launch_k##K##_m##M##_enc(a, stream);

@@ -65,6 +65,22 @@ struct FixedArgs {
     // (K, m) codes any k <= K: its steps x >= k read zeros (encode: out-of-range DMA; decode: the
     // position tables, K wide, mark them erased).
     int k_rt;
+    // Var-k batches (cauchy_256_*_var): group g owns input blocks first[g] .. first[g + 1] - 1 of a
+    // packed array of total_blocks blocks (nullptr = the uniform layout above). Only the kernels'
+    // var instantiations read these.
+    const int *first;
+    int total_blocks;
 };
+
+// Group g of a var-k batch: its first block and k_g = first[g + 1] - first[g]. A group whose k_g
+// lies outside 2..kmax or whose span leaves [0, total] is malformed: k = 0, f = 0, false.
+__device__ __forceinline__ bool var_group(const int *first, int g, int kmax, int total, int &f, int &k) {
+    const int f0 = first[g], f1 = first[g + 1];
+    const long long kk = static_cast<long long>(f1) - f0;
+    const bool ok = f0 >= 0 && f1 <= total && kk >= 2 && kk <= kmax;
+    f = ok ? f0 : 0;
+    k = ok ? static_cast<int>(kk) : 0;
+    return ok;
+}
 
 }  // namespace sh

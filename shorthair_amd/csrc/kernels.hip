@@ -80,7 +80,9 @@ __device__ __forceinline__ void store_col(uint8_t *sb, int q, const LaneCol &c, 
 // R output rows per launch row-chunk (grid.y). PER_GROUP: coefficients differ per group and the
 // wave must hold a single group (grid.z = group); otherwise lanes are flattened over (g, q).
 // ---------------------------------------------------------------------------------------------
-template <int R, bool PER_GROUP>
+// VAR: a var-k batch (ApplyArgs::first): the group's input base is first[g] * in_bstride and its
+// input count its own k (encode; decode's per-group coefficients are zero past it already).
+template <int R, bool PER_GROUP, bool VAR = false>
 __global__ __launch_bounds__(256) void apply_generic(ApplyArgs a) {
     int g, q;
     if (PER_GROUP) {
@@ -102,6 +104,13 @@ __global__ __launch_bounds__(256) void apply_generic(ApplyArgs a) {
     const LaneCol col = lane_col(q, geo);
     const bool bytewise = geo.sub < 4;
     const uint8_t *in_g = a.in + static_cast<long long>(g) * a.in_gstride;
+    int n_in = a.n_in;
+    if constexpr (VAR) {
+        int f, kg;
+        var_group(a.first, g, a.n_in, a.total_blocks, f, kg);  // malformed: kg = 0, nothing is read
+        in_g = a.in + static_cast<long long>(f) * a.in_bstride;
+        n_in = kg;
+    }
     const uint8_t *coef = a.coef + (PER_GROUP ? static_cast<long long>(g) * a.coef_gstride : 0) +
                           static_cast<long long>(o0) * a.coef_ld;
 
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(256) void apply_generic(ApplyArgs a) {
 #pragma unroll
         for (int b = 0; b < 8; ++b) acc[o][b] = 0;
 
-    for (int j4 = 0; j4 < a.n_in; j4 += 4) {
+    for (int j4 = 0; j4 < n_in; j4 += 4) {
         uint32_t cw[R];
 #pragma unroll
         for (int o = 0; o < R; ++o)
@@ -119,7 +128,7 @@ __global__ __launch_bounds__(256) void apply_generic(ApplyArgs a) {
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
             const int j = j4 + jj;
-            if (j >= a.n_in) break;
+            if (j >= n_in) break;
             uint32_t any = 0;
 #pragma unroll
             for (int o = 0; o < R; ++o) any |= (cw[o] >> (8 * jj)) & 0xffu;
@@ -216,6 +225,42 @@ __global__ __launch_bounds__(256) void copy_first(const uint8_t *in, long long i
     out[g * out_gstride + r] = in[g * in_gstride + p];
 }
 
+// Var-k m = 1 encode: xor_rows over the group's own blocks first[g] .. first[g + 1] - 1.
+__global__ __launch_bounds__(256) void xor_rows_var(const uint8_t *in, const int *first, int total_blocks, int kmax,
+                                                    uint8_t *out, long long out_gstride, int B, int groups) {
+    const int nw = (B + 3) / 4;
+    const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int g = static_cast<int>(t / nw);
+    const int w = static_cast<int>(t - static_cast<long long>(g) * nw);
+    if (g >= groups) return;
+    int f, n_in;
+    var_group(first, g, kmax, total_blocks, f, n_in);  // malformed: n_in = 0, zeros
+    const int nb = min(4, B - 4 * w);
+    const uint8_t *src = in + static_cast<long long>(f) * B + 4 * w;
+    uint8_t *dst = out + g * out_gstride + 4 * w;
+    if (nb == 4) {
+        uint32_t x = 0;
+        for (int j = 0; j < n_in; ++j) x ^= ld32(src + static_cast<long long>(j) * B);
+        st32(dst, x);
+    } else {
+        for (int i = 0; i < nb; ++i) {
+            uint8_t x = 0;
+            for (int j = 0; j < n_in; ++j) x ^= src[static_cast<long long>(j) * B + i];
+            dst[i] = x;
+        }
+    }
+}
+
+// Var-k encode: count the malformed groups (their recovery blocks are zeros) into *errors.
+__global__ __launch_bounds__(256) void var_check(const int *first, int total_blocks, int kmax, int groups,
+                                                 int *errors) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    int f, kg;
+    const bool bad = g < groups && !var_group(first, g, kmax, total_blocks, f, kg);
+    const int n = __popcll(__ballot(bad));
+    if (n && (threadIdx.x & 63) == 0) atomicAdd(errors, n);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Decode setup, one 64-lane workgroup (one wave) per group. Restates the reference's
 // sort_blocks + generate_bitmatrix (cauchy_256.cpp:522-554, :691-774) in GF(256):
@@ -254,12 +299,34 @@ struct SetupScratch {
 
 // W groups per workgroup (one wave each): the exp/log tables are staged once per workgroup
 // ((28,4,256), 209,263 groups: one wave per workgroup spent 0.28 ms of a 0.81 ms decode).
-template <int W>
+// Malformed group of a var-k batch (fixed-kernel mode: lanes l, l + L, .. of its group): count -1,
+// empty position tables (stage A then reads nothing of it), counted.
+template <int L>
+__device__ __forceinline__ void var_group_fail(const DecodeSetupArgs &a, int g, int l) {
+    if (a.coefA == nullptr) {
+        const int KP = a.kp, MP = (a.m + 3) & ~3;
+        for (int x = l; x < KP; x += L) a.pos[static_cast<long long>(g) * KP + x] = 0xFF;
+        for (int y = l; y < MP; y += L) a.rpos[static_cast<long long>(g) * MP + y] = 0xFF;
+    }
+    if (l == 0) {
+        a.e_out[g] = -1;
+        if (a.errors) atomicAdd(a.errors, 1);
+    }
+}
+
+// VAR (all three setups): a var-k batch (DecodeSetupArgs::first). The group's k and rows base are
+// its own; KT = a.k (kmax) stays the width of the generator rows and X' table.
+template <int W, bool VAR = false>
 __global__ __launch_bounds__(64 * W, 8) void decode_setup(DecodeSetupArgs a, int groups) {
     const int wave = threadIdx.x >> 6;
     const int g = blockIdx.x * W + wave;
     const int lane = threadIdx.x & 63;
-    const int k = a.k, m = a.m;
+    const int KT = a.k, m = a.m;
+    int k = KT, vfirst = 0;
+    bool vok = true;
+    if constexpr (VAR) {
+        if (g < groups) vok = var_group(a.first, g, KT, a.total_blocks, vfirst, k);
+    }
     // exp over [0, 1024): every exponent sum of the closed form's coefficients, [1, 763], without a
     // mod-255 reduction (s_exp[i] = exp(i mod 255))
     __shared__ uint8_t s_exp[1024];
@@ -274,7 +341,7 @@ __global__ __launch_bounds__(64 * W, 8) void decode_setup(DecodeSetupArgs a, int
     // Every global load of the staging is issued before any is waited for (one round trip): the
     // group's row bytes as dwords where aligned, four exp entries per thread.
     if (g < groups) {
-        const uint8_t *rows = a.rows + static_cast<long long>(g) * a.rows_gstride;
+        const uint8_t *rows = VAR ? a.rows + vfirst : a.rows + static_cast<long long>(g) * a.rows_gstride;
         if ((k & 3) == 0 && (reinterpret_cast<uintptr_t>(rows) & 3) == 0) {
             if (4 * lane < k)
                 *reinterpret_cast<uint32_t *>(S.rows + 4 * lane) = *reinterpret_cast<const uint32_t *>(rows + 4 * lane);
@@ -293,13 +360,17 @@ __global__ __launch_bounds__(64 * W, 8) void decode_setup(DecodeSetupArgs a, int
     }
     for (int i = threadIdx.x; i < 256; i += 64 * W) s_log[i] = static_cast<uint8_t>(a.gf_log[i]);
     if (m <= 6) {
-        for (int i = threadIdx.x; i < (m - 1) * k; i += 64 * W) s_gen[i] = a.gen[i];
+        for (int i = threadIdx.x; i < (m - 1) * KT; i += 64 * W) s_gen[i] = a.gen[i];
     } else {
-        for (int i = threadIdx.x; i < k; i += 64 * W) s_xp[i] = a.xp[i];
+        for (int i = threadIdx.x; i < KT; i += 64 * W) s_xp[i] = a.xp[i];
         for (int i = threadIdx.x; i < m; i += 64 * W) s_yp[i] = a.yp[i];
     }
     __syncthreads();  // the only workgroup barrier: waves below may return independently
     if (g >= groups) return;
+    if (VAR && !vok) {
+        var_group_fail<64>(a, g, lane);
+        return;
+    }
     auto present = [&](int r) { return static_cast<int>((S.present[r >> 2] >> (8 * (r & 3))) & 0xFFu); };
     for (int j = lane; j < k; j += 64)  // a row occurs at most k <= 255 times: no carry between counts
         atomicAdd(&S.present[S.rows[j] >> 2], 1u << (8 * (S.rows[j] & 3)));
@@ -372,7 +443,7 @@ __global__ __launch_bounds__(64 * W, 8) void decode_setup(DecodeSetupArgs a, int
         era[i] = S.era[i];
     }
     auto C = [&](int r, int x) -> uint32_t {
-        return r == 0 ? 1u : (m <= 6 ? s_gen[(r - 1) * k + x] : a.gen[static_cast<long long>(r - 1) * k + x]);
+        return r == 0 ? 1u : (m <= 6 ? s_gen[(r - 1) * KT + x] : a.gen[static_cast<long long>(r - 1) * KT + x]);
     };
 
     // Stage-A coefficients (generic path only), row-major [i][j], leading dimension ldA.
@@ -582,17 +653,16 @@ __device__ __forceinline__ unsigned group_ballot(bool p, int gb) {
 // Before the workgroup's staging barrier: the group's row bytes (all loads in flight together),
 // present bitmap cleared.
 template <int L, class GS>
-__device__ __forceinline__ void group_load_rows(const DecodeSetupArgs &a, int g, int l, GS &S) {
-    const uint8_t *rows = a.rows + static_cast<long long>(g) * a.rows_gstride;
-    for (int j = l; j < a.k; j += L) S.rows[j] = rows[j];
+__device__ __forceinline__ void group_load_rows(const uint8_t *rows, int k, int l, GS &S) {
+    for (int j = l; j < k; j += L) S.rows[j] = rows[j];
     for (int t = l; t < 8; t += L) S.present[t] = 0;
 }
 
 // After the barrier: malformed check, ordered compaction, position tables, e and the per-group
 // lists. Returns e when coefficients remain to be written, 0 when the group is done.
 template <int L, int EC, class GS>
-__device__ int group_prologue(const DecodeSetupArgs &a, int g, int l, int gb, GS &S) {
-    const int k = a.k, m = a.m;
+__device__ int group_prologue(const DecodeSetupArgs &a, int g, int k, int l, int gb, GS &S) {
+    const int m = a.m;
     // A row listed twice, or a recovery row past the generator, is outside the reference's
     // contract (decode_setup above): the group is left untouched and reported.
     bool bad = false;
@@ -691,26 +761,35 @@ struct Row12 {
     }
 };
 
-template <int W>
+template <int W, bool VAR = false>
 __global__ __launch_bounds__(64 * W, 8) void decode_setup_small(DecodeSetupArgs a, int groups) {
     constexpr int L = 8;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int sub = lane / L, l = lane % L, gb = L * sub;  // gb: first lane of this group
     const int g = (blockIdx.x * W + wave) * (64 / L) + sub;
-    const int k = a.k, m = a.m;
+    const int KT = a.k, m = a.m;
+    int k = KT, vfirst = 0;
+    bool vok = true;
+    if constexpr (VAR) {
+        if (g < groups) vok = var_group(a.first, g, KT, a.total_blocks, vfirst, k);
+    }
     __shared__ uint8_t s_exp[512];
     __shared__ uint8_t s_log[256];
     __shared__ uint8_t s_gen[5 * 256];
     __shared__ GroupScratch<8, 8> sw[(64 / L) * W];
     GroupScratch<8, 8> &S = sw[(64 / L) * wave + sub];
     const bool live = g < groups;
-    if (live) group_load_rows<L>(a, g, l, S);
+    if (live) group_load_rows<L>(VAR ? a.rows + vfirst : a.rows + static_cast<long long>(g) * a.rows_gstride, k, l, S);
     for (int i = threadIdx.x; i < 512; i += 64 * W) s_exp[i] = a.gf_exp[i];
     for (int i = threadIdx.x; i < 256; i += 64 * W) s_log[i] = static_cast<uint8_t>(a.gf_log[i]);
-    for (int i = threadIdx.x; i < (m - 1) * k; i += 64 * W) s_gen[i] = a.gen[i];
+    for (int i = threadIdx.x; i < (m - 1) * KT; i += 64 * W) s_gen[i] = a.gen[i];
     __syncthreads();  // the only workgroup barrier: groups below may finish independently
     if (!live) return;
-    const int e = group_prologue<L, 8>(a, g, l, gb, S);
+    if (VAR && !vok) {
+        var_group_fail<L>(a, g, l);
+        return;
+    }
+    const int e = group_prologue<L, 8>(a, g, k, l, gb, S);
     if (e == 0) return;
     const int emax = a.emax;
     uint8_t *Bc = a.targets ? nullptr : a.coefB + static_cast<long long>(g) * a.coefB_gstride;
@@ -735,7 +814,7 @@ __global__ __launch_bounds__(64 * W, 8) void decode_setup_small(DecodeSetupArgs 
 #pragma unroll
         for (int c = 0; c < 12; ++c) {
             uint32_t v = 0u;
-            if (c < e) v = r == 0 ? 1u : s_gen[(r - 1) * k + S.era[c]];
+            if (c < e) v = r == 0 ? 1u : s_gen[(r - 1) * KT + S.era[c]];
             else if (c < 2 * e) v = c - e == l ? 1u : 0u;
             u.or_byte(c, v);
         }
@@ -785,14 +864,19 @@ struct CauchyLists {
     uint8_t x[EC], y[EC], la[EC], lb[EC];
 };
 
-template <int W, int L>
+template <int W, int L, bool VAR = false>
 __global__ __launch_bounds__(64 * W, 8) void decode_setup_cauchy(DecodeSetupArgs a, int groups) {
     static_assert(L % 8 == 0 && L <= 32, "group lanes: a multiple of 8, at most 32");
     constexpr int GPW = 64 / L;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int sub = lane / L, l = lane % L, gb = L * sub;
     const int g = (blockIdx.x * W + wave) * GPW + sub;
-    const int k = a.k, m = a.m;
+    const int KT = a.k, m = a.m;
+    int k = KT, vfirst = 0;
+    bool vok = true;
+    if constexpr (VAR) {
+        if (g < groups) vok = var_group(a.first, g, KT, a.total_blocks, vfirst, k);
+    }
     __shared__ uint8_t s_exp[1024];  // exp(i mod 255): exponent sums up to 763 unreduced
     __shared__ uint8_t s_log[256];
     __shared__ uint8_t s_xp[256], s_yp[256];
@@ -801,7 +885,7 @@ __global__ __launch_bounds__(64 * W, 8) void decode_setup_cauchy(DecodeSetupArgs
     GroupScratch<L, 256> &S = sw[GPW * wave + sub];
     CauchyLists<L> &X = cw[GPW * wave + sub];
     const bool live = g < groups;
-    if (live) group_load_rows<L>(a, g, l, S);
+    if (live) group_load_rows<L>(VAR ? a.rows + vfirst : a.rows + static_cast<long long>(g) * a.rows_gstride, k, l, S);
     static_assert(64 * W * 4 >= 1024, "four exp entries per thread");
     {
         uint8_t ev[4];
@@ -811,11 +895,15 @@ __global__ __launch_bounds__(64 * W, 8) void decode_setup_cauchy(DecodeSetupArgs
         for (int u = 0; u < 4; ++u) s_exp[4 * threadIdx.x + u] = ev[u];
     }
     for (int i = threadIdx.x; i < 256; i += 64 * W) s_log[i] = static_cast<uint8_t>(a.gf_log[i]);
-    for (int i = threadIdx.x; i < k; i += 64 * W) s_xp[i] = a.xp[i];
+    for (int i = threadIdx.x; i < KT; i += 64 * W) s_xp[i] = a.xp[i];
     for (int i = threadIdx.x; i < m; i += 64 * W) s_yp[i] = a.yp[i];
     __syncthreads();  // the only workgroup barrier: groups below may finish independently
     if (!live) return;
-    const int e = group_prologue<L, L>(a, g, l, gb, S);
+    if (VAR && !vok) {
+        var_group_fail<L>(a, g, l);
+        return;
+    }
+    const int e = group_prologue<L, L>(a, g, k, l, gb, S);
     if (e == 0) return;
     for (int t = l; t < e; t += L) {
         X.x[t] = s_xp[S.era[t]];
@@ -1002,13 +1090,16 @@ __global__ __launch_bounds__(256) void fill_pcg(uint8_t *out, long long gstride,
 template <int R, bool PG>
 static hipError_t launch_apply_t(const ApplyArgs &a, hipStream_t stream) {
     const int row_chunks = (a.n_out + R - 1) / R;
+    const bool var = a.first != nullptr;
     if (PG) {
         dim3 grid((a.geo.nq + 63) / 64, row_chunks, a.groups);
-        hipLaunchKernelGGL((apply_generic<R, true>), grid, dim3(64), 0, stream, a);
+        hipLaunchKernelGGL((var ? apply_generic<R, true, true> : apply_generic<R, true, false>), grid, dim3(64), 0,
+                           stream, a);
     } else {
         const long long cols = static_cast<long long>(a.groups) * a.geo.nq;
         dim3 grid(static_cast<unsigned>((cols + 255) / 256), row_chunks, 1);
-        hipLaunchKernelGGL((apply_generic<R, false>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((var ? apply_generic<R, false, true> : apply_generic<R, false, false>), grid, dim3(256), 0,
+                           stream, a);
     }
     return hipGetLastError();
 }
@@ -1023,6 +1114,21 @@ hipError_t launch_xor_rows(const uint8_t *in, long long in_gstride, int n_in, ui
     const long long n = static_cast<long long>(groups) * ((B + 3) / 4);
     hipLaunchKernelGGL(xor_rows, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream,
                        in, in_gstride, n_in, out, out_gstride, B, groups);
+    return hipGetLastError();
+}
+
+hipError_t launch_xor_rows_var(const uint8_t *in, const int *first, int total_blocks, int kmax, uint8_t *out,
+                               long long out_gstride, int B, int groups, hipStream_t stream) {
+    const long long n = static_cast<long long>(groups) * ((B + 3) / 4);
+    hipLaunchKernelGGL(xor_rows_var, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, stream, in, first,
+                       total_blocks, kmax, out, out_gstride, B, groups);
+    return hipGetLastError();
+}
+
+hipError_t launch_var_check(const int *first, int total_blocks, int kmax, int groups, int *errors,
+                            hipStream_t stream) {
+    hipLaunchKernelGGL(var_check, dim3((groups + 255) / 256), dim3(256), 0, stream, first, total_blocks, kmax,
+                       groups, errors);
     return hipGetLastError();
 }
 
@@ -1044,19 +1150,21 @@ hipError_t launch_decode_setup(const DecodeSetupArgs &a, int groups, hipStream_t
     static const bool wave_only = measure_int(SH_MEASURE_ENV("SH_SETUP_WAVE"), 0) != 0;
     static const int min_small = measure_int(SH_MEASURE_ENV("SH_SETUP_MIN_SMALL"), 8192);
     static const int min_cauchy = measure_int(SH_MEASURE_ENV("SH_SETUP_MIN_CAUCHY"), 8192);
+    const bool var = a.first != nullptr;  // var-k batches: the same three setups, VAR instantiations
     if (a.coefA == nullptr && !wave_only) {
         if (a.m <= 6 && groups >= min_small) {
-            hipLaunchKernelGGL(decode_setup_small<W>, dim3((groups + 8 * W - 1) / (8 * W)), dim3(64 * W), 0,
-                               stream, a, groups);
+            hipLaunchKernelGGL((var ? decode_setup_small<W, true> : decode_setup_small<W, false>),
+                               dim3((groups + 8 * W - 1) / (8 * W)), dim3(64 * W), 0, stream, a, groups);
             return hipGetLastError();
         }
         if (a.m >= 7 && a.emax <= 16 && groups >= min_cauchy) {
-            hipLaunchKernelGGL((decode_setup_cauchy<W, 16>), dim3((groups + 4 * W - 1) / (4 * W)), dim3(64 * W), 0,
-                               stream, a, groups);
+            hipLaunchKernelGGL((var ? decode_setup_cauchy<W, 16, true> : decode_setup_cauchy<W, 16, false>),
+                               dim3((groups + 4 * W - 1) / (4 * W)), dim3(64 * W), 0, stream, a, groups);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL(decode_setup<W>, dim3((groups + W - 1) / W), dim3(64 * W), 0, stream, a, groups);
+    hipLaunchKernelGGL((var ? decode_setup<W, true> : decode_setup<W, false>), dim3((groups + W - 1) / W),
+                       dim3(64 * W), 0, stream, a, groups);
     return hipGetLastError();
 }
 

@@ -25,6 +25,11 @@ struct ApplyArgs {
     const uint64_t *rowbytes;  // 256 entries: byte b = c * 2^b in GF(256)/0x187
     int groups;
     Geometry geo;
+    // Var-k batches (nullptr = the uniform layout): group g's inputs are blocks first[g] ..
+    // first[g + 1] - 1 of a packed array of total_blocks blocks; n_in is then the largest k allowed
+    // (kmax). A malformed group (var_group, geometry.hpp) reads nothing.
+    const int *first;
+    int total_blocks;
 };
 
 struct DecodeSetupArgs {
@@ -57,6 +62,12 @@ struct DecodeSetupArgs {
     uint64_t *targets;      // [G][ldB/8][emax][8]: address of the stage-B snippet of S^-1[j][i] at [j/8][i][j%8]
     uint64_t snip_base;     // address of snippet 0 (stage-B snippet table, stride SNIP_STRIDE)
     int *errors;            // device counter: groups with more recovery blocks than erasures
+    // Var-k batches (nullptr = uniform): group g has k_g = first[g + 1] - first[g] rows starting at
+    // rows + first[g]; k above is then kmax, the width of gen / xp and the bound of k_g. A
+    // malformed group (var_group, geometry.hpp) gets e_out = -1, empty position tables and is
+    // counted in `errors`.
+    const int *first;
+    int total_blocks;
 };
 
 struct ScatterArgs {
@@ -196,6 +207,12 @@ bool has_fixed(int k, int m, int B);
 int fixed_kernel_k(int k, int m, int B);
 
 hipError_t launch_apply(const ApplyArgs &a, bool per_group, hipStream_t stream);
+// Var-k m = 1 encode: group g XORs its blocks first[g] .. first[g + 1] - 1 (malformed: zeros).
+hipError_t launch_xor_rows_var(const uint8_t *in, const int *first, int total_blocks, int kmax, uint8_t *out,
+                               long long out_gstride, int B, int groups, hipStream_t stream);
+// Var-k encode: adds the number of malformed groups to *errors (the decode setup does it for decode).
+hipError_t launch_var_check(const int *first, int total_blocks, int kmax, int groups, int *errors,
+                            hipStream_t stream);
 hipError_t launch_xor_rows(const uint8_t *in, long long in_gstride, int n_in, uint8_t *out,
                            long long out_gstride, int B, int groups, hipStream_t stream);
 hipError_t launch_copy_first(const uint8_t *in, long long in_gstride, uint8_t *out,

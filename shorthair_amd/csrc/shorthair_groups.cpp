@@ -4,8 +4,11 @@
 // (:580-609) for many groups per call. Receiver: RecoverGroup (:704-761) over the packets OnData
 // (:764-902) keeps, for many groups per call.
 //
-// Layer above the public batch ABI (cauchy_256_batch.h): groups are bucketed by (k, m, B), a
-// bucket is cut into chunks of ~chunk_bytes() of blocks, and chunks alternate between two pinned
+// Layer above the public batch ABI (cauchy_256_batch.h): groups are bucketed by (K, m, B) -- K the
+// compiled kernel's k that codes the group (sh::fixed_kernel_k), or the group's own k without one
+// -- so groups that would each run the same compiled kernel for the same K steps share a var-k
+// launch (cauchy_256_*_var, blocks framed packed with first[] alongside); a bucket with a single
+// distinct k makes the uniform call. A bucket is cut into chunks of ~chunk_bytes() of blocks, and chunks alternate between two pinned
 // staging slots. For chunk i the host threads frame the blocks into slot i%2 while the GPU runs
 // chunk i-1 (H2D, kernel, D2H on one stream); once slot i%2's previous chunk has completed its
 // outputs are unframed on the host threads. So host framing, PCIe and kernels overlap, and the
@@ -15,6 +18,7 @@
 #include <emmintrin.h>
 
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +31,7 @@
 #include <vector>
 
 #include "../../include/cauchy_256_batch.h"
+#include "kernels.hpp"
 #include "measure.hpp"
 #include "../../include/shorthair_groups.h"
 
@@ -266,6 +271,37 @@ int pipeline(Staging &st, int chunks, size_t slot_bytes, Prep prepare, Submit su
     return err;
 }
 
+// shorthair_groups_stats: batched codec launches issued and groups coded by them.
+std::atomic<long long> g_launches{0}, g_groups{0};
+void count_launch(int groups) {
+    g_launches.fetch_add(1, std::memory_order_relaxed);
+    g_groups.fetch_add(groups, std::memory_order_relaxed);
+}
+
+// Bucket key of a group: the K of the compiled kernel that codes (k, m, B), or k itself.
+int bucket_k(int k, int m, int B) {
+    const int K = sh::fixed_kernel_k(k, m, B);
+    return K > 0 ? K : k;
+}
+
+// Chunks of a var-k bucket: groups [start[c], start[c + 1]) of `ids`, cut so that a chunk's blocks
+// plus per_group_out bytes per group stay within chunk_bytes() (at least one group per chunk).
+std::vector<int> var_chunks(const std::vector<int> &ids, const std::function<int(int)> &k_of, int B,
+                            size_t per_group_out) {
+    std::vector<int> start{0};
+    size_t bytes = 0;
+    for (int j = 0; j < static_cast<int>(ids.size()); ++j) {
+        const size_t need = static_cast<size_t>(k_of(ids[j])) * B + per_group_out;
+        if (j > start.back() && bytes + need > chunk_bytes()) {
+            start.push_back(j);
+            bytes = 0;
+        }
+        bytes += need;
+    }
+    start.push_back(static_cast<int>(ids.size()));
+    return start;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Sender
 // ---------------------------------------------------------------------------------------------
@@ -320,7 +356,7 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
             }
         } else {
             g.out_stride = 3 + t.B;
-            buckets[std::make_tuple(t.k, t.m, t.B)].push_back(i);
+            buckets[std::make_tuple(bucket_k(t.k, t.m, t.B), t.m, t.B)].push_back(i);
         }
     }
     if (buckets.empty()) return 0;
@@ -328,8 +364,74 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
     std::lock_guard<std::mutex> lock(st.mu);
     if (int rc = ensure_staging(st)) return rc;
     for (auto &kv : buckets) {
-        const int k = std::get<0>(kv.first), m = std::get<1>(kv.first), B = std::get<2>(kv.first);
+        const int m = std::get<1>(kv.first), B = std::get<2>(kv.first);
         const std::vector<int> &ids = kv.second;
+        int k = info[ids[0]].k, kmax = k;
+        bool mixed = false;
+        for (int id : ids) {
+            mixed |= info[id].k != k;
+            kmax = std::max(kmax, info[id].k);
+        }
+        if (mixed) {
+            // One var-k launch per chunk. Slot: blocks packed | recovery [gn][m][B] | first[gn + 1]
+            const size_t out_g = static_cast<size_t>(m) * B;
+            const std::vector<int> start = var_chunks(ids, [&](int id) { return info[id].k; }, B, out_g + 4);
+            const int chunks = static_cast<int>(start.size()) - 1;
+            size_t max_blocks = 0, max_gn = 0;
+            std::vector<std::vector<int>> first(chunks);
+            for (int c = 0; c < chunks; ++c) {
+                first[c].push_back(0);
+                for (int j = start[c]; j < start[c + 1]; ++j) first[c].push_back(first[c].back() + info[ids[j]].k);
+                max_blocks = std::max<size_t>(max_blocks, first[c].back());
+                max_gn = std::max<size_t>(max_gn, start[c + 1] - start[c]);
+            }
+            const size_t o_out = (max_blocks * B + 15) & ~size_t(15), o_first = o_out + max_gn * out_g;
+            const size_t slot_bytes = o_first + (max_gn + 1) * sizeof(int);
+            auto prepare = [&](int c, Slot &s) {
+                const int g0 = start[c], gn = start[c + 1] - g0;
+                uint8_t *h = static_cast<uint8_t *>(s.h);
+                std::memcpy(h + o_first, first[c].data(), (gn + 1) * sizeof(int));
+                parallel_for(gn, [&](int j) {
+                    const ShorthairTxGroup &g = groups[ids[g0 + j]];
+                    uint8_t *blk = h + static_cast<size_t>(first[c][j]) * B;
+                    for (int x = 0; x < g.k; ++x, blk += B) {  // EncodeQueued :540-557, as below
+                        const int len = g.lens[x];
+                        put_u16(blk, len);
+                        framing_copy(blk + 2, static_cast<const uint8_t *>(g.packets[x]), len);
+                        std::memset(blk + 2 + len, 0, B - 2 - len);
+                    }
+                    framing_fence();
+                });
+            };
+            auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
+                const int g0 = start[c], gn = start[c + 1] - g0, total = first[c].back();
+                uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
+                SG_CHECK(hipMemcpyAsync(d, h, static_cast<size_t>(total) * B, hipMemcpyHostToDevice, st.stream));
+                SG_CHECK(hipMemcpyAsync(d + o_first, h + o_first, (gn + 1) * sizeof(int), hipMemcpyHostToDevice,
+                                        st.stream));
+                const int rc = cauchy_256_encode_batch_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + o_first),
+                                                           total, d, d + o_out, st.stream);
+                if (rc != 0) return rc;
+                count_launch(gn);
+                SG_CHECK(hipMemcpyAsync(h + o_out, d + o_out, gn * out_g, hipMemcpyDeviceToHost, st.stream));
+                fin = [&, g0, gn, h]() {
+                    parallel_for(gn, [&](int j) {  // GenerateRecoveryBlock :598-608, as below
+                        ShorthairTxGroup &g = groups[ids[g0 + j]];
+                        const uint8_t *rec = h + o_out + static_cast<size_t>(j) * out_g;
+                        for (int y = 0; y < m; ++y) {
+                            uint8_t *p = g.out + static_cast<size_t>(y) * g.out_stride;
+                            p[0] = static_cast<uint8_t>(g.k + y);
+                            p[1] = static_cast<uint8_t>(g.k - 1);
+                            p[2] = static_cast<uint8_t>(m - 1);
+                            std::memcpy(p + 3, rec + static_cast<size_t>(y) * B, B);
+                        }
+                    });
+                };
+                return 0;
+            };
+            if (int rc = pipeline(st, chunks, slot_bytes, prepare, submit)) return rc;
+            continue;
+        }
         const size_t in_g = static_cast<size_t>(k) * B, out_g = static_cast<size_t>(m) * B;
         const int per = static_cast<int>(std::max<size_t>(1, chunk_bytes() / (in_g + out_g)));
         const int n = static_cast<int>(ids.size());
@@ -358,6 +460,7 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
             SG_CHECK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st.stream));
             const int rc = cauchy_256_encode_batch(k, m, B, gn, d, d + in_bytes, st.stream);
             if (rc != 0) return rc;
+            count_launch(gn);
             SG_CHECK(hipMemcpyAsync(h + in_bytes, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, st.stream));
             fin = [&, g0, gn, h, in_bytes]() {
                 // GenerateRecoveryBlock :598-608: "[k+i][k-1][m-1][block i]"
@@ -439,7 +542,9 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
             if (on_packet) on_packet(cb_ctx, i, 0, g.rec_packets[0] + 2, g.rec_lens[0] - 2);
             ++decoded;
         } else if (kind[i] == 1) {
-            buckets[std::make_tuple(info[i].k, info[i].m, info[i].B)].push_back(i);
+            buckets[std::make_tuple(info[i].m >= 2 ? bucket_k(info[i].k, info[i].m, info[i].B) : info[i].k,
+                                    info[i].m, info[i].B)]
+                .push_back(i);
         }
     }
     if (buckets.empty()) return decoded;
@@ -447,8 +552,96 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
     std::lock_guard<std::mutex> lock(st.mu);
     if (int rc = ensure_staging(st)) return rc;
     for (auto &kv : buckets) {
-        const int k = std::get<0>(kv.first), m = std::get<1>(kv.first), B = std::get<2>(kv.first);
+        const int m = std::get<1>(kv.first), B = std::get<2>(kv.first);
         const std::vector<int> &ids = kv.second;
+        int k = info[ids[0]].k, kmax = k;
+        bool mixed = false;
+        for (int id : ids) {
+            mixed |= info[id].k != k;
+            kmax = std::max(kmax, info[id].k);
+        }
+        if (mixed) {  // m >= 2 (bucket key)
+            // One var-k launch per chunk. Slot: blocks packed | rows packed | out [gn][emax][B] |
+            // out rows [gn][emax] | count [gn] | first[gn + 1]
+            const int emax = std::min(kmax, m);
+            const size_t out_g = static_cast<size_t>(emax) * B;
+            const std::vector<int> start = var_chunks(ids, [&](int id) { return info[id].k; }, B,
+                                                      out_g + emax + 8 + 256);
+            const int chunks = static_cast<int>(start.size()) - 1;
+            size_t max_blocks = 0, max_gn = 0;
+            std::vector<std::vector<int>> first(chunks);
+            for (int c = 0; c < chunks; ++c) {
+                first[c].push_back(0);
+                for (int j = start[c]; j < start[c + 1]; ++j) first[c].push_back(first[c].back() + info[ids[j]].k);
+                max_blocks = std::max<size_t>(max_blocks, first[c].back());
+                max_gn = std::max<size_t>(max_gn, start[c + 1] - start[c]);
+            }
+            const size_t o_rows = max_blocks * B, o_out = (o_rows + max_blocks + 15) & ~size_t(15);
+            const size_t o_orow = o_out + max_gn * out_g, o_cnt = (o_orow + max_gn * emax + 3) & ~size_t(3);
+            const size_t o_first = o_cnt + max_gn * sizeof(int);
+            const size_t slot_bytes = o_first + (max_gn + 1) * sizeof(int);
+            auto prepare = [&](int c, Slot &s) {
+                const int g0 = start[c], gn = start[c + 1] - g0;
+                uint8_t *h = static_cast<uint8_t *>(s.h);
+                std::memcpy(h + o_first, first[c].data(), (gn + 1) * sizeof(int));
+                parallel_for(gn, [&](int j) {
+                    const ShorthairRxGroup &g = groups[ids[g0 + j]];
+                    const RxInfo &r = info[ids[g0 + j]];
+                    uint8_t *blk = h + static_cast<size_t>(first[c][j]) * B;
+                    uint8_t *rows = h + o_rows + first[c][j];
+                    int x = 0;
+                    for (int i = 0; i < g.n_orig; ++i, ++x, blk += B) {  // RecoverGroup :710-725, as below
+                        const int len = g.orig_lens[i];
+                        put_u16(blk, len);
+                        framing_copy(blk + 2, static_cast<const uint8_t *>(g.orig_data[i]), len);
+                        std::memset(blk + 2 + len, 0, B - 2 - len);
+                        rows[x] = g.orig_ids[i];
+                    }
+                    for (int i = 0; i < r.use; ++i, ++x, blk += B) {  // :727-735
+                        framing_copy(blk, g.rec_packets[i] + 3, B);
+                        rows[x] = g.rec_packets[i][0];
+                    }
+                    framing_fence();
+                });
+            };
+            auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
+                const int g0 = start[c], gn = start[c + 1] - g0, total = first[c].back();
+                uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
+                SG_CHECK(hipMemcpyAsync(d, h, static_cast<size_t>(total) * B, hipMemcpyHostToDevice, st.stream));
+                SG_CHECK(hipMemcpyAsync(d + o_rows, h + o_rows, total, hipMemcpyHostToDevice, st.stream));
+                SG_CHECK(hipMemcpyAsync(d + o_first, h + o_first, (gn + 1) * sizeof(int), hipMemcpyHostToDevice,
+                                        st.stream));
+                const int rc = cauchy_256_decode_batch_out_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + o_first),
+                                                               total, d, d + o_rows, d + o_out, d + o_orow,
+                                                               reinterpret_cast<int *>(d + o_cnt), st.stream);
+                if (rc != 0) return rc;
+                count_launch(gn);
+                SG_CHECK(hipMemcpyAsync(h + o_out, d + o_out, gn * out_g, hipMemcpyDeviceToHost, st.stream));
+                SG_CHECK(hipMemcpyAsync(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax), hipMemcpyDeviceToHost,
+                                        st.stream));
+                if (!on_packet) {
+                    fin = [] {};
+                    return 0;
+                }
+                fin = [&, g0, gn, h]() {
+                    for (int j = 0; j < gn; ++j) {  // RecoverGroup :741-756, as below
+                        const int gi = ids[g0 + j];
+                        const int e = info[gi].k - groups[gi].n_orig;
+                        const uint8_t *out = h + o_out + static_cast<size_t>(j) * out_g;
+                        for (int i = 0; i < e; ++i) {
+                            const uint8_t *blk = out + static_cast<size_t>(i) * B;
+                            const int id = h[o_orow + static_cast<size_t>(j) * emax + i];
+                            const int len = static_cast<int>(get_u16(blk));
+                            if (len <= B - 2) on_packet(cb_ctx, gi, id, blk + 2, len);
+                        }
+                    }
+                };
+                return 0;
+            };
+            if (int rc = pipeline(st, chunks, slot_bytes, prepare, submit)) return rc;
+            decoded += static_cast<int>(ids.size());
+            continue;
+        }
         const int emax = std::min(k, m);
         // per group: blocks k*B, rows k; out emax*B; out rows emax; count 4 (m >= 2 only)
         const size_t in_g = static_cast<size_t>(k) * B;
@@ -496,6 +689,7 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
                 const int rc = cauchy_256_decode_batch_out(k, m, B, gn, d, d + o_rows, d + o_out, d + o_orow,
                                                            reinterpret_cast<int *>(d + o_cnt), st.stream);
                 if (rc != 0) return rc;
+                count_launch(gn);
                 SG_CHECK(hipMemcpyAsync(h + o_out, d + o_out, gn * out_g, hipMemcpyDeviceToHost, st.stream));
                 SG_CHECK(hipMemcpyAsync(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax),
                                         hipMemcpyDeviceToHost, st.stream));
@@ -504,6 +698,7 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
                 // single recovery block (n_orig = k-1 originals precede it)
                 const int rc = cauchy_256_decode_batch(k, m, B, gn, d, d + o_rows, st.stream);
                 if (rc != 0) return rc;
+                count_launch(gn);
                 SG_CHECK(hipMemcpy2DAsync(h + o_out, B, d + static_cast<size_t>(k - 1) * B, in_g, B, gn,
                                           hipMemcpyDeviceToHost, st.stream));
             }
@@ -539,4 +734,10 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
         decoded += n;
     }
     return decoded;
+}
+
+extern "C" int shorthair_groups_stats(long long *launches, long long *groups) {
+    if (launches) *launches = g_launches.load(std::memory_order_relaxed);
+    if (groups) *groups = g_groups.load(std::memory_order_relaxed);
+    return 0;
 }

@@ -54,11 +54,14 @@ struct TShape {
     static_assert(AHEAD >= 1 && AHEAD * DPW < 64, "ring schedule");
 };
 
-template <class S, bool DEC>
+// VAR: the var-k source form (FixedArgs::first), as fixed::Src's: per-chunk group base relative to
+// the tile's window, and encode steps past the chunk's own k read zeros.
+template <class S, bool DEC, bool VAR = false>
 struct TSrc {
     __amdgpu_buffer_rsrc_t rsrc;
     uint32_t dbase[S::DPW];
     int dgl[S::DPW];
+    int kc[S::DPW];  // VAR encode: k of the chunk's group
     uint32_t B;
     int wave, n, x0, k, kp, pstride, row0;
     uint32_t rd;
@@ -69,7 +72,17 @@ struct TSrc {
                                          const uint8_t *lds_pos) {
         const FixedArgs &a = t.f;
         const Geometry &geo = a.geo;
-        rsrc = fixed::wg_rsrc(a.in, a.in_bytes, a.in_gstride, w.g_first);
+        int f0 = 0;
+        if constexpr (VAR) {
+            f0 = fixed::var_window(a, w.g_first, t.k);
+            if (f0 == 0x7FFFFFFF) f0 = 0;  // no well-formed group: every chunk below is OOR
+            const long long start = static_cast<long long>(f0) * geo.B;
+            long long nb = a.in_bytes - start;
+            nb = nb < 0 ? 0 : (nb > 0x7FFFFFFFll ? 0x7FFFFFFFll : nb);
+            rsrc = fixed::make_rsrc(a.in + start, static_cast<uint32_t>(nb));
+        } else {
+            rsrc = fixed::wg_rsrc(a.in, a.in_bytes, a.in_gstride, w.g_first);
+        }
         B = geo.B;
         lds = lds_ring;
         pos = lds_pos;
@@ -91,9 +104,14 @@ struct TSrc {
             const int gx = colx >= 0 ? static_cast<int>(colx / geo.nq) : -1;
             const int qx = static_cast<int>(colx - static_cast<long long>(gx) * geo.nq);
             dgl[j] = gx - w.g_first;
-            dbase[j] = (colx >= w.lo && colx < w.hi)
-                           ? static_cast<uint32_t>(gx - w.g_first) * gstride + fixed::col_off(qx, geo) + aa * geo.sub
-                           : OOR;
+            if constexpr (VAR) {
+                const uint32_t gb = fixed::var_base(a, gx, colx >= w.lo && colx < w.hi, t.k, f0, kc[j]);
+                dbase[j] = gb == OOR ? OOR : gb + fixed::col_off(qx, geo) + aa * geo.sub;
+            } else {
+                dbase[j] = (colx >= w.lo && colx < w.hi)
+                               ? static_cast<uint32_t>(gx - w.g_first) * gstride + fixed::col_off(qx, geo) + aa * geo.sub
+                               : OOR;
+            }
         }
     }
 
@@ -112,7 +130,7 @@ struct TSrc {
                     const int t = gx < k ? gx : kp + row0 + (gx - k);
                     const int p = pos[dgl[j] * pstride + t];
                     o = p == 0xFF ? OOR : dbase[j] + static_cast<uint32_t>(p) * B;
-                } else {
+                } else if (!VAR || gx < kc[j]) {
                     o = dbase[j];
                     so = static_cast<uint32_t>(gx) * B;
                 }
@@ -309,7 +327,7 @@ __device__ __forceinline__ void store_rows_rot(const Snk &sink, int nr, int y0, 
     }
 }
 
-template <class S, bool DEC, bool COL>
+template <class S, bool DEC, bool COL, bool VAR = false>
 __device__ __forceinline__ void tile_body(const TileArgs &t) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const FixedArgs &a = t.f;
@@ -348,7 +366,7 @@ __device__ __forceinline__ void tile_body(const TileArgs &t) {
         }
         __syncthreads();
     }
-    TSrc<S, DEC> src;
+    TSrc<S, DEC, VAR> src;
     src.init(t, w, lds, lds_pos);
     RowSink<S> sink;
     FixedArgs so = a;  // this slice's partial output
@@ -432,6 +450,18 @@ __device__ __forceinline__ void tile_body(const TileArgs &t) {
     }                                                                                             \
     __global__ __launch_bounds__(64 * CW * P) void tile_col_dec_p##P(TileArgs t) {                \
         tile_body<TShape<P, CW>, true, true>(t);                                                  \
+    }                                                                                             \
+    __global__ __launch_bounds__(64 * CW * P) void tile_encv_p##P(TileArgs t) {                   \
+        tile_body<TShape<P, CW>, false, false, true>(t);                                          \
+    }                                                                                             \
+    __global__ __launch_bounds__(64 * CW * P) void tile_decv_p##P(TileArgs t) {                   \
+        tile_body<TShape<P, CW>, true, false, true>(t);                                           \
+    }                                                                                             \
+    __global__ __launch_bounds__(64 * CW * P) void tile_col_encv_p##P(TileArgs t) {               \
+        tile_body<TShape<P, CW>, false, true, true>(t);                                           \
+    }                                                                                             \
+    __global__ __launch_bounds__(64 * CW * P) void tile_col_decv_p##P(TileArgs t) {               \
+        tile_body<TShape<P, CW>, true, true, true>(t);                                            \
     }
 // Part counts whose workgroups fill the CU's 4 SIMDs evenly (P * CW a multiple of 4; tile_parts)
 SH_TILE_KERNEL(1, 4)
@@ -509,6 +539,9 @@ hipError_t launch_tile(const TileArgs &t, bool dec, hipStream_t s) {
     switch (tile_parts(t.nrows)) {
 #define SH_L(P, CW)                                                                              \
     case P:                                                                                      \
+        if (t.f.first)                                                                           \
+            return t.col ? tile::launch_p<P, CW>(t, dec, s, tile::tile_col_encv_p##P, tile::tile_col_decv_p##P) \
+                         : tile::launch_p<P, CW>(t, dec, s, tile::tile_encv_p##P, tile::tile_decv_p##P); \
         return t.col ? tile::launch_p<P, CW>(t, dec, s, tile::tile_col_enc_p##P, tile::tile_col_dec_p##P) \
                      : tile::launch_p<P, CW>(t, dec, s, tile::tile_enc_p##P, tile::tile_dec_p##P);
         SH_L(1, 4) SH_L(2, 4) SH_L(4, 2) SH_L(6, 2) SH_L(8, 2) SH_L(12, 1) SH_L(16, 1)

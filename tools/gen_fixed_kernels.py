@@ -741,6 +741,20 @@ def gen_config(k, m):
                        f"{'false' if 'nodma' in ABLATE else 'true'}, {'true' if stream_mode(P) else 'false'}, "
                        f"{parts_per_wg(P)}, {blk_sub(k, m)}, {1 if split[mode] else 0})\n"))
         paths.append(path)
+        # The var-k form (FIXED_KERNEL_VAR: per-group source base and k, cauchy_256_*_var) in a
+        # translation unit of its own, over the same generated program. The measurement-only
+        # sources and launch forms have none: their launcher reports "not supported".
+        var_ok = not (pers[mode] or stream_mode(P) or blk_sub(k, m) or "nodma" in ABLATE
+                      or parts_per_wg(P) != P)
+        path = os.path.join(OUTDIR, f"fixed_{name}_{mode}v.hip")
+        with open(path, "w") as f:
+            f.write(f"// GENERATED by tools/gen_fixed_kernels.py -- do not edit. (k={k}, m={m}, {mode}, var-k)\n"
+                    f'#include "fixed_{name}.inc"\n'
+                    + (f"FIXED_KERNEL_VAR({name}, {k}, {m}, {P}, {CW}, {R}, {minw}, {mode}, {dec})\n" if var_ok else
+                       "namespace sh {\nnamespace fixed {\n"
+                       f"hipError_t launch_{name}_{mode}v(FixedArgs, hipStream_t) {{ return hipErrorNotSupported; }}\n"
+                       "}\n}\n"))
+        paths.append(path)
     return paths
 
 

@@ -83,6 +83,20 @@ int shorthair_recover_groups(const ShorthairRxGroup *groups, int count, shorthai
  * Returns 0. */
 int shorthair_groups_stats(long long *launches, long long *groups);
 
+/* Where the two calls above turn payloads into code blocks. 0 = on host threads, into the pinned
+ * staging buffer (the default): the whole blocks, zero padding included, cross PCIe. 1 = on the GPU
+ * (shorthair_frame_batch, shorthair_frame.h): the pinned buffer carries only the payload bytes packed
+ * back to back plus 12-14 bytes of offsets, lengths and rows per block, and the blocks are built in
+ * device memory. Buckets, chunks, launches, wire bytes, return codes and delivery order are the same
+ * on both routes; k == 1 groups never reach the GPU on either.
+ * Returns the previous value, -1 for any other argument (nothing changes). Read once at the start of
+ * each shorthair_*_groups call. */
+int shorthair_groups_set_framing(int where);
+
+/* Cumulative bytes the two calls copied host->device and device->host since load. Either pointer may
+ * be NULL. Returns 0. */
+int shorthair_groups_traffic(long long *h2d_bytes, long long *d2h_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ import os
 
 __all__ = ["lib", "Block", "CAUCHY_256_VERSION", "cauchy_256_init", "cauchy_256_encode",
            "cauchy_256_decode", "encode_batch", "decode_batch", "decode_batch_out",
-           "encode_batch_var", "decode_batch_out_var", "groups_stats",
+           "encode_batch_var", "decode_batch_out_var", "frame_batch", "groups_stats",
            "fill_synthetic", "erasure_pattern", "batch_reserve", "batch_errors", "has_fixed", "path", "default_stream", "sync", "LIB_PATH",
            "EXPORTED_SYMBOLS"]
 
@@ -22,7 +22,7 @@ CAUCHY_256_VERSION = 2
 LIB_PATH = os.environ.get("SH_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                          "libcauchy256.so")
 
-# Every function declared in include/*.h (cauchy_256.h, cauchy_256_batch.h, gf256.h).
+# Every function declared in include/*.h.
 EXPORTED_SYMBOLS = [
     "_cauchy_256_init", "cauchy_256_encode", "cauchy_256_decode",
     "cauchy_256_batch_init", "cauchy_256_encode_batch", "cauchy_256_decode_batch",
@@ -34,7 +34,8 @@ EXPORTED_SYMBOLS = [
     "gf256_init_", "gf256_add_mem", "gf256_add2_mem", "gf256_addset_mem", "gf256_mul_mem",
     "gf256_muladd_mem", "gf256_memswap",
     "shorthair_recovery_packet_bytes", "shorthair_encode_groups", "shorthair_recover_groups",
-    "shorthair_groups_stats",
+    "shorthair_groups_stats", "shorthair_groups_set_framing", "shorthair_groups_traffic",
+    "shorthair_frame_batch",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -77,6 +78,8 @@ lib.cauchy_256_encode_batch_var.argtypes = [_c.c_int] * 4 + [_c.c_void_p, _c.c_i
 lib.cauchy_256_encode_batch_var.restype = _c.c_int
 lib.cauchy_256_decode_batch_out_var.argtypes = [_c.c_int] * 4 + [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 6
 lib.cauchy_256_decode_batch_out_var.restype = _c.c_int
+lib.shorthair_frame_batch.argtypes = [_c.c_int, _c.c_int, _c.c_void_p, _c.c_longlong] + [_c.c_void_p] * 5
+lib.shorthair_frame_batch.restype = _c.c_int
 lib.shorthair_groups_stats.argtypes = [_c.c_void_p, _c.c_void_p]
 lib.shorthair_groups_stats.restype = _c.c_int
 lib.cauchy_256_batch_reserve.argtypes = [_c.c_int] * 4
@@ -179,6 +182,18 @@ def decode_batch_out_var(kmax, m, block_bytes, groups, first, total_blocks, bloc
                                                       _ptr(blocks), _ptr(rows), _ptr(out), _ptr(out_rows),
                                                       _ptr(out_count), _stream(stream)),
                   "decode_batch_out_var")
+
+
+def frame_batch(block_bytes, total_blocks, payload, payload_bytes, off, length, raw, blocks, stream=None):
+    """Frame payloads into code blocks on the GPU (include/shorthair_frame.h): block j of blocks
+    [total_blocks][B] = [len u16 LE][payload[off[j] : off[j] + length[j]]][zeros], or the B bytes at
+    off[j] verbatim where raw[j] != 0. payload uint8, off int64 [total_blocks], length int32
+    [total_blocks], raw uint8 [total_blocks] or None, blocks uint8 (8-byte aligned): cuda tensors, or
+    integer device addresses."""
+    def ptr(t):
+        return t if t is None or isinstance(t, int) else int(t.data_ptr())
+    return _check(lib.shorthair_frame_batch(block_bytes, total_blocks, ptr(payload), payload_bytes, ptr(off),
+                                            ptr(length), ptr(raw), ptr(blocks), _stream(stream)), "frame_batch")
 
 
 def groups_stats():

@@ -22,8 +22,10 @@
 
 #include "../../include/cauchy_256.h"
 #include "../../include/cauchy_256_batch.h"
+#include "../../include/shorthair_frame.h"
 #include "cauchy_math.hpp"
 #include "colsnip.h"
+#include "frame.hpp"
 #include "kernels.hpp"
 #include "measure.hpp"
 
@@ -1105,6 +1107,26 @@ extern "C" int cauchy_256_decode_batch_out_var(int kmax, int m, int block_bytes,
     w.e = d_out_count;
     return decode_core(c, kmax, m, block_bytes, groups, static_cast<const uint8_t *>(d_blocks), d_rows, w,
                        ls.errors, static_cast<uint8_t *>(d_out), s, nullptr, false, &var);
+}
+
+extern "C" int shorthair_frame_batch(int block_bytes, int total_blocks, const void *d_payload,
+                                     long long payload_bytes, const long long *d_off, const int *d_len,
+                                     const unsigned char *d_raw, void *d_blocks, void *stream) {
+    if (block_bytes < 8 || block_bytes % 8 != 0 || total_blocks < 0 || payload_bytes < 0) return -1;
+    if (total_blocks > 0 && (!d_payload || !d_off || !d_len || !d_blocks)) return -1;
+    if (reinterpret_cast<uintptr_t>(d_blocks) % 8 != 0) return -1;
+    if (total_blocks == 0) return 0;
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    hipStream_t s = pick(stream);
+    StreamState *st = stream_state(c, s);
+    if (!st) return -2;
+    // under the stream's lock, like the var-k encode's count (encode_batch_var)
+    std::lock_guard<std::mutex> g(st->mu);
+    SH_CHECK(sh::launch_frame(block_bytes, total_blocks, static_cast<const uint8_t *>(d_payload), payload_bytes,
+                              d_off, d_len, d_raw, static_cast<uint8_t *>(d_blocks), st->d_errors, s));
+    return 0;
 }
 
 extern "C" int cauchy_256_batch_reserve(int k, int m, int block_bytes, int groups) {

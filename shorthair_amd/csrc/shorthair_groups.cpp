@@ -13,6 +13,10 @@
 // chunk i-1 (H2D, kernel, D2H on one stream); once slot i%2's previous chunk has completed its
 // outputs are unframed on the host threads. So host framing, PCIe and kernels overlap, and the
 // only host work per byte is the framing copy the reference also does (its memset/memcpy).
+//
+// shorthair_groups_set_framing(1) moves the framing to the GPU ("Device framing" below): the host
+// threads then pack only the payload bytes into the pinned slot, shorthair_frame_batch builds the
+// blocks in device memory, and everything else -- buckets, chunks, codec calls, finishers -- is shared.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 #include <emmintrin.h>
@@ -31,6 +35,7 @@
 #include <vector>
 
 #include "../../include/cauchy_256_batch.h"
+#include "../../include/shorthair_frame.h"
 #include "kernels.hpp"
 #include "measure.hpp"
 #include "../../include/shorthair_groups.h"
@@ -205,21 +210,24 @@ Staging &staging() {
     return s;
 }
 
-int ensure_slot(Slot &s, size_t bytes) {
+// nh pinned bytes and nd device bytes: equal on the host-framing route (the slot is mirrored); on the
+// device-framing route the pinned side holds payload bytes and outputs only, the device side the
+// framed blocks as well.
+int ensure_slot(Slot &s, size_t nh, size_t nd) {
     if (!s.ev) SG_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (bytes > s.nh) {
+    if (nh > s.nh) {
         if (s.h) (void)hipHostFree(s.h);
         s.h = nullptr;
         s.nh = 0;
-        SG_CHECK(hipHostMalloc(&s.h, bytes, hipHostMallocDefault));
-        s.nh = bytes;
+        SG_CHECK(hipHostMalloc(&s.h, nh, hipHostMallocDefault));
+        s.nh = nh;
     }
-    if (bytes > s.nd) {
+    if (nd > s.nd) {
         if (s.d) (void)hipFree(s.d);
         s.d = nullptr;
         s.nd = 0;
-        SG_CHECK(hipMalloc(&s.d, bytes));
-        s.nd = bytes;
+        SG_CHECK(hipMalloc(&s.d, nd));
+        s.nd = nd;
     }
     return 0;
 }
@@ -245,12 +253,12 @@ int drain(Slot &s) {
 // Run `chunks` chunks through the two slots: prepare(i, slot) frames chunk i into the slot's
 // pinned buffer, submit(i, slot) enqueues its copies and kernels and returns the finisher.
 template <class Prep, class Submit>
-int pipeline(Staging &st, int chunks, size_t slot_bytes, Prep prepare, Submit submit) {
+int pipeline(Staging &st, int chunks, size_t slot_h, size_t slot_d, Prep prepare, Submit submit) {
     int err = 0;
     for (int i = 0; i < chunks && !err; ++i) {
         Slot &s = st.slot[i & 1];
         if ((err = drain(s))) break;
-        if ((err = ensure_slot(s, slot_bytes))) break;
+        if ((err = ensure_slot(s, slot_h, slot_d))) break;
         prepare(i, s);
         std::function<void()> fin;
         if ((err = submit(i, s, fin))) break;
@@ -277,6 +285,20 @@ void count_launch(int groups) {
     g_launches.fetch_add(1, std::memory_order_relaxed);
     g_groups.fetch_add(groups, std::memory_order_relaxed);
 }
+
+// shorthair_groups_traffic: bytes the two calls copied host->device and device->host.
+std::atomic<long long> g_h2d{0}, g_d2h{0};
+hipError_t copy_h2d(void *dst, const void *src, size_t n, hipStream_t stream) {
+    g_h2d.fetch_add(static_cast<long long>(n), std::memory_order_relaxed);
+    return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, stream);
+}
+hipError_t copy_d2h(void *dst, const void *src, size_t n, hipStream_t stream) {
+    g_d2h.fetch_add(static_cast<long long>(n), std::memory_order_relaxed);
+    return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, stream);
+}
+
+// shorthair_groups_set_framing: 0 = host threads frame the blocks, 1 = the GPU does.
+std::atomic<int> g_framing{0};
 
 // Bucket key of a group: the K of the compiled kernel that codes (k, m, B), or k itself.
 int bucket_k(int k, int m, int B) {
@@ -322,6 +344,130 @@ bool tx_info(const ShorthairTxGroup &g, TxInfo &t) {
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Device framing (shorthair_groups_set_framing(1)). A chunk's pinned slot carries only what the GPU
+// cannot know, back to back, and goes over in one H2D copy:
+//   off[nb] (8 B each) | len[nb] (4 B) | first[gn + 1] (4 B, mixed-k buckets) | rows[nb] | raw[nb]
+//   (receiver) | pad to 16 | the payload bytes packed (recovery bodies among them, raw = 1)
+// shorthair_frame_batch builds blocks[nb][B] from it in a device-only region behind the copy, the
+// codec call of the host-framing route runs on those blocks, and the outputs follow them. The
+// pinned side holds the outputs right behind the copy (DevLayout::h2d rounded up to 16).
+// Buckets, chunk cuts (device bytes of blocks + outputs), launches and finishers are those of the
+// host-framing route.
+// ---------------------------------------------------------------------------------------------
+struct DevLayout {
+    size_t o_len, o_first, o_rows, o_raw, o_pay, h2d;  // h2d = o_pay + payload bytes
+};
+inline size_t up16(size_t x) { return (x + 15) & ~size_t(15); }
+DevLayout dev_layout(size_t nb, size_t gn, size_t pay, bool mixed, bool rx) {
+    DevLayout L;
+    L.o_len = 8 * nb;
+    L.o_first = L.o_len + 4 * nb;
+    L.o_rows = L.o_first + (mixed ? 4 * (gn + 1) : 0);
+    L.o_raw = L.o_rows + (rx ? nb : 0);
+    L.o_pay = up16(L.o_raw + (rx ? nb : 0));
+    L.h2d = L.o_pay + pay;
+    return L;
+}
+
+// Chunk c of a bucket is groups [start[c], start[c + 1]) of `ids`; blk0[j] / pay0[j] are the first
+// block and the first payload byte of group j counted from the bucket's start.
+struct DevChunks {
+    std::vector<int> start;
+    std::vector<long long> blk0, pay0;
+    int chunks() const { return static_cast<int>(start.size()) - 1; }
+    int g0(int c) const { return start[c]; }
+    int gn(int c) const { return start[c + 1] - start[c]; }
+    int nb(int c) const { return static_cast<int>(blk0[start[c + 1]] - blk0[start[c]]); }
+    size_t pay(int c) const { return static_cast<size_t>(pay0[start[c + 1]] - pay0[start[c]]); }
+};
+std::vector<int> uniform_chunks(int n, int per) {
+    std::vector<int> start;
+    for (int g = 0; g < n; g += per) start.push_back(g);
+    start.push_back(n);
+    return start;
+}
+
+int encode_bucket_dev(Staging &st, ShorthairTxGroup *groups, const std::vector<TxInfo> &info,
+                      const std::vector<int> &ids, int m, int B, int k, int kmax, bool mixed) {
+    const int n = static_cast<int>(ids.size());
+    const size_t out_g = static_cast<size_t>(m) * B;
+    DevChunks ch;
+    if (mixed)
+        ch.start = var_chunks(ids, [&](int id) { return info[id].k; }, B, out_g + 4);
+    else
+        ch.start = uniform_chunks(n, static_cast<int>(std::max<size_t>(1, chunk_bytes() / (static_cast<size_t>(k) * B + out_g))));
+    ch.blk0.assign(n + 1, 0);
+    ch.pay0.assign(n + 1, 0);
+    for (int j = 0; j < n; ++j) {
+        const ShorthairTxGroup &g = groups[ids[j]];
+        long long p = 0;
+        for (int x = 0; x < g.k; ++x) p += g.lens[x];
+        ch.blk0[j + 1] = ch.blk0[j] + g.k;
+        ch.pay0[j + 1] = ch.pay0[j] + p;
+    }
+    size_t nh = 0, nd = 0;
+    for (int c = 0; c < ch.chunks(); ++c) {
+        const size_t head = up16(dev_layout(ch.nb(c), ch.gn(c), ch.pay(c), mixed, false).h2d);
+        nh = std::max(nh, head + ch.gn(c) * out_g);
+        nd = std::max(nd, head + static_cast<size_t>(ch.nb(c)) * B + ch.gn(c) * out_g);
+    }
+    auto prepare = [&](int c, Slot &s) {
+        const int g0 = ch.g0(c), gn = ch.gn(c);
+        const DevLayout L = dev_layout(ch.nb(c), gn, ch.pay(c), mixed, false);
+        uint8_t *h = static_cast<uint8_t *>(s.h);
+        long long *off = reinterpret_cast<long long *>(h);
+        int *len = reinterpret_cast<int *>(h + L.o_len), *first = reinterpret_cast<int *>(h + L.o_first);
+        if (mixed)
+            for (int j = 0; j <= gn; ++j) first[j] = static_cast<int>(ch.blk0[g0 + j] - ch.blk0[g0]);
+        parallel_for(gn, [&](int j) {
+            const ShorthairTxGroup &g = groups[ids[g0 + j]];
+            const long long b = ch.blk0[g0 + j] - ch.blk0[g0];
+            long long p = ch.pay0[g0 + j] - ch.pay0[g0];
+            for (int x = 0; x < g.k; ++x) {  // EncodeQueued :540-557: the payload only; the GPU frames it
+                const int l = g.lens[x];
+                off[b + x] = p;
+                len[b + x] = l;
+                framing_copy(h + L.o_pay + p, static_cast<const uint8_t *>(g.packets[x]), l);
+                p += l;
+            }
+            framing_fence();
+        });
+    };
+    auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
+        const int g0 = ch.g0(c), gn = ch.gn(c), nb = ch.nb(c);
+        const DevLayout L = dev_layout(nb, gn, ch.pay(c), mixed, false);
+        uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
+        const size_t o_blk = up16(L.h2d), o_out = o_blk + static_cast<size_t>(nb) * B, h_out = up16(L.h2d);
+        SG_CHECK(copy_h2d(d, h, L.h2d, st.stream));
+        int rc = shorthair_frame_batch(B, nb, d + L.o_pay, static_cast<long long>(ch.pay(c)),
+                                       reinterpret_cast<const long long *>(d), reinterpret_cast<const int *>(d + L.o_len),
+                                       nullptr, d + o_blk, st.stream);
+        if (rc != 0) return rc;
+        rc = mixed ? cauchy_256_encode_batch_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + L.o_first), nb,
+                                                 d + o_blk, d + o_out, st.stream)
+                   : cauchy_256_encode_batch(k, m, B, gn, d + o_blk, d + o_out, st.stream);
+        if (rc != 0) return rc;
+        count_launch(gn);
+        SG_CHECK(copy_d2h(h + h_out, d + o_out, gn * out_g, st.stream));
+        fin = [&, g0, gn, h, h_out, out_g]() {
+            parallel_for(gn, [&](int j) {  // GenerateRecoveryBlock :598-608: "[k+i][k-1][m-1][block i]"
+                ShorthairTxGroup &g = groups[ids[g0 + j]];
+                const uint8_t *rec = h + h_out + static_cast<size_t>(j) * out_g;
+                for (int y = 0; y < m; ++y) {
+                    uint8_t *p = g.out + static_cast<size_t>(y) * g.out_stride;
+                    p[0] = static_cast<uint8_t>(g.k + y);
+                    p[1] = static_cast<uint8_t>(g.k - 1);
+                    p[2] = static_cast<uint8_t>(m - 1);
+                    std::memcpy(p + 3, rec + static_cast<size_t>(y) * B, B);
+                }
+            });
+        };
+        return 0;
+    };
+    return pipeline(st, ch.chunks(), nh, nd, prepare, submit);
+}
+
 }  // namespace
 
 extern "C" int shorthair_recovery_packet_bytes(int k, const unsigned short *lens) {
@@ -333,6 +479,7 @@ extern "C" int shorthair_recovery_packet_bytes(int k, const unsigned short *lens
 
 extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
     if (count < 0 || (count > 0 && !groups)) return -1;
+    const int framing = g_framing.load(std::memory_order_relaxed);
     std::vector<TxInfo> info(count);
     for (int i = 0; i < count; ++i) {
         if (!tx_info(groups[i], info[i])) return -1;
@@ -372,6 +519,10 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
             mixed |= info[id].k != k;
             kmax = std::max(kmax, info[id].k);
         }
+        if (framing == 1) {
+            if (int rc = encode_bucket_dev(st, groups, info, ids, m, B, k, kmax, mixed)) return rc;
+            continue;
+        }
         if (mixed) {
             // One var-k launch per chunk. Slot: blocks packed | recovery [gn][m][B] | first[gn + 1]
             const size_t out_g = static_cast<size_t>(m) * B;
@@ -406,14 +557,13 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
             auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
                 const int g0 = start[c], gn = start[c + 1] - g0, total = first[c].back();
                 uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-                SG_CHECK(hipMemcpyAsync(d, h, static_cast<size_t>(total) * B, hipMemcpyHostToDevice, st.stream));
-                SG_CHECK(hipMemcpyAsync(d + o_first, h + o_first, (gn + 1) * sizeof(int), hipMemcpyHostToDevice,
-                                        st.stream));
+                SG_CHECK(copy_h2d(d, h, static_cast<size_t>(total) * B, st.stream));
+                SG_CHECK(copy_h2d(d + o_first, h + o_first, (gn + 1) * sizeof(int), st.stream));
                 const int rc = cauchy_256_encode_batch_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + o_first),
                                                            total, d, d + o_out, st.stream);
                 if (rc != 0) return rc;
                 count_launch(gn);
-                SG_CHECK(hipMemcpyAsync(h + o_out, d + o_out, gn * out_g, hipMemcpyDeviceToHost, st.stream));
+                SG_CHECK(copy_d2h(h + o_out, d + o_out, gn * out_g, st.stream));
                 fin = [&, g0, gn, h]() {
                     parallel_for(gn, [&](int j) {  // GenerateRecoveryBlock :598-608, as below
                         ShorthairTxGroup &g = groups[ids[g0 + j]];
@@ -429,7 +579,7 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
                 };
                 return 0;
             };
-            if (int rc = pipeline(st, chunks, slot_bytes, prepare, submit)) return rc;
+            if (int rc = pipeline(st, chunks, slot_bytes, slot_bytes, prepare, submit)) return rc;
             continue;
         }
         const size_t in_g = static_cast<size_t>(k) * B, out_g = static_cast<size_t>(m) * B;
@@ -457,11 +607,11 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
             const int g0 = c * per, gn = std::min(per, n - g0);
             uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
             const size_t in_bytes = gn * in_g, out_bytes = gn * out_g;
-            SG_CHECK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st.stream));
+            SG_CHECK(copy_h2d(d, h, in_bytes, st.stream));
             const int rc = cauchy_256_encode_batch(k, m, B, gn, d, d + in_bytes, st.stream);
             if (rc != 0) return rc;
             count_launch(gn);
-            SG_CHECK(hipMemcpyAsync(h + in_bytes, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, st.stream));
+            SG_CHECK(copy_d2h(h + in_bytes, d + in_bytes, out_bytes, st.stream));
             fin = [&, g0, gn, h, in_bytes]() {
                 // GenerateRecoveryBlock :598-608: "[k+i][k-1][m-1][block i]"
                 parallel_for(gn, [&](int j) {
@@ -478,7 +628,7 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
             };
             return 0;
         };
-        if (int rc = pipeline(st, chunks, slot_bytes, prepare, submit)) return rc;
+        if (int rc = pipeline(st, chunks, slot_bytes, slot_bytes, prepare, submit)) return rc;
     }
     return 0;
 }
@@ -525,11 +675,139 @@ int rx_info(const ShorthairRxGroup &g, RxInfo &r) {
     return 1;
 }
 
+// Device framing, receiver (layout above): originals as payload bytes, the recovery packets' bodies
+// as raw blocks.
+int recover_bucket_dev(Staging &st, const ShorthairRxGroup *groups, const std::vector<RxInfo> &info,
+                       const std::vector<int> &ids, int m, int B, int k, int kmax, bool mixed,
+                       shorthair_on_packet_fn on_packet, void *cb_ctx) {
+    const int n = static_cast<int>(ids.size());
+    const int emax = std::min(mixed ? kmax : k, m);
+    const size_t out_g = m >= 2 ? static_cast<size_t>(emax) * B : static_cast<size_t>(B);
+    DevChunks ch;
+    if (mixed) {
+        ch.start = var_chunks(ids, [&](int id) { return info[id].k; }, B, out_g + emax + 8 + 256);
+    } else {
+        const size_t per_g = static_cast<size_t>(k) * B + k + out_g + emax + 4;
+        ch.start = uniform_chunks(n, static_cast<int>(std::max<size_t>(1, chunk_bytes() / per_g)));
+    }
+    ch.blk0.assign(n + 1, 0);
+    ch.pay0.assign(n + 1, 0);
+    for (int j = 0; j < n; ++j) {
+        const ShorthairRxGroup &g = groups[ids[j]];
+        const RxInfo &r = info[ids[j]];
+        long long p = static_cast<long long>(r.use) * B;
+        for (int i = 0; i < g.n_orig; ++i) p += g.orig_lens[i];
+        ch.blk0[j + 1] = ch.blk0[j] + r.k;
+        ch.pay0[j + 1] = ch.pay0[j] + p;
+    }
+    size_t nh = 0, nd = 0;
+    for (int c = 0; c < ch.chunks(); ++c) {
+        const size_t head = up16(dev_layout(ch.nb(c), ch.gn(c), ch.pay(c), mixed, true).h2d);
+        const size_t outs = ch.gn(c) * out_g + static_cast<size_t>(ch.gn(c)) * emax;
+        nh = std::max(nh, head + outs);
+        nd = std::max(nd, head + static_cast<size_t>(ch.nb(c)) * B + outs + 4 + ch.gn(c) * sizeof(int));
+    }
+    auto prepare = [&](int c, Slot &s) {
+        const int g0 = ch.g0(c), gn = ch.gn(c);
+        const DevLayout L = dev_layout(ch.nb(c), gn, ch.pay(c), mixed, true);
+        uint8_t *h = static_cast<uint8_t *>(s.h);
+        long long *off = reinterpret_cast<long long *>(h);
+        int *len = reinterpret_cast<int *>(h + L.o_len), *first = reinterpret_cast<int *>(h + L.o_first);
+        uint8_t *rows = h + L.o_rows, *raw = h + L.o_raw;
+        if (mixed)
+            for (int j = 0; j <= gn; ++j) first[j] = static_cast<int>(ch.blk0[g0 + j] - ch.blk0[g0]);
+        parallel_for(gn, [&](int j) {
+            const ShorthairRxGroup &g = groups[ids[g0 + j]];
+            const RxInfo &r = info[ids[g0 + j]];
+            long long x = ch.blk0[g0 + j] - ch.blk0[g0];
+            long long p = ch.pay0[g0 + j] - ch.pay0[g0];
+            for (int i = 0; i < g.n_orig; ++i, ++x) {  // RecoverGroup :710-725: the payload only
+                const int l = g.orig_lens[i];
+                off[x] = p;
+                len[x] = l;
+                raw[x] = 0;
+                rows[x] = g.orig_ids[i];
+                framing_copy(h + L.o_pay + p, static_cast<const uint8_t *>(g.orig_data[i]), l);
+                p += l;
+            }
+            for (int i = 0; i < r.use; ++i, ++x) {  // :727-735: the packet's block, verbatim
+                off[x] = p;
+                len[x] = B;
+                raw[x] = 1;
+                rows[x] = g.rec_packets[i][0];
+                framing_copy(h + L.o_pay + p, g.rec_packets[i] + 3, B);
+                p += B;
+            }
+            framing_fence();
+        });
+    };
+    auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
+        const int g0 = ch.g0(c), gn = ch.gn(c), nb = ch.nb(c);
+        const DevLayout L = dev_layout(nb, gn, ch.pay(c), mixed, true);
+        uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
+        const size_t o_blk = up16(L.h2d), o_out = o_blk + static_cast<size_t>(nb) * B;
+        const size_t o_orow = o_out + gn * out_g, o_cnt = (o_orow + static_cast<size_t>(gn) * emax + 3) & ~size_t(3);
+        const size_t h_out = up16(L.h2d), h_orow = h_out + gn * out_g;
+        SG_CHECK(copy_h2d(d, h, L.h2d, st.stream));
+        int rc = shorthair_frame_batch(B, nb, d + L.o_pay, static_cast<long long>(ch.pay(c)),
+                                       reinterpret_cast<const long long *>(d), reinterpret_cast<const int *>(d + L.o_len),
+                                       d + L.o_raw, d + o_blk, st.stream);
+        if (rc != 0) return rc;
+        if (m >= 2) {
+            rc = mixed ? cauchy_256_decode_batch_out_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + L.o_first), nb,
+                                                         d + o_blk, d + L.o_rows, d + o_out, d + o_orow,
+                                                         reinterpret_cast<int *>(d + o_cnt), st.stream)
+                       : cauchy_256_decode_batch_out(k, m, B, gn, d + o_blk, d + L.o_rows, d + o_out, d + o_orow,
+                                                     reinterpret_cast<int *>(d + o_cnt), st.stream);
+            if (rc != 0) return rc;
+            count_launch(gn);
+            SG_CHECK(copy_d2h(h + h_out, d + o_out, gn * out_g, st.stream));
+            SG_CHECK(copy_d2h(h + h_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
+        } else {
+            // m == 1 (a uniform bucket): the one erasure lands in place in block k-1 of each group
+            rc = cauchy_256_decode_batch(k, m, B, gn, d + o_blk, d + L.o_rows, st.stream);
+            if (rc != 0) return rc;
+            count_launch(gn);
+            SG_CHECK(hipMemcpy2DAsync(h + h_out, B, d + o_blk + static_cast<size_t>(k - 1) * B, static_cast<size_t>(k) * B,
+                                      B, gn, hipMemcpyDeviceToHost, st.stream));
+            g_d2h.fetch_add(static_cast<long long>(gn) * B, std::memory_order_relaxed);
+        }
+        if (!on_packet) {
+            fin = [] {};
+            return 0;
+        }
+        fin = [&, g0, gn, h, h_out, h_orow, out_g, emax]() {
+            for (int j = 0; j < gn; ++j) {  // RecoverGroup :741-756: deliver blocks whose length prefix fits
+                const int gi = ids[g0 + j];
+                const ShorthairRxGroup &g = groups[gi];
+                const int kg = info[gi].k, e = kg - g.n_orig;
+                const uint8_t *out = h + h_out + static_cast<size_t>(j) * out_g;
+                int missing = -1;
+                if (m < 2) {
+                    bool seen[256] = {false};
+                    for (int i = 0; i < g.n_orig; ++i) seen[g.orig_ids[i]] = true;
+                    for (int x = 0; x < kg && missing < 0; ++x)
+                        if (!seen[x]) missing = x;
+                }
+                for (int i = 0; i < e; ++i) {
+                    const uint8_t *blk = out + static_cast<size_t>(i) * B;
+                    const int id = m >= 2 ? h[h_orow + static_cast<size_t>(j) * emax + i] : missing;
+                    const int len = static_cast<int>(get_u16(blk));
+                    if (len <= B - 2) on_packet(cb_ctx, gi, id, blk + 2, len);
+                }
+            }
+        };
+        return 0;
+    };
+    return pipeline(st, ch.chunks(), nh, nd, prepare, submit);
+}
+
 }  // namespace
 
 extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int count,
                                         shorthair_on_packet_fn on_packet, void *cb_ctx) {
     if (count < 0 || (count > 0 && !groups)) return -1;
+    const int framing = g_framing.load(std::memory_order_relaxed);
     std::vector<RxInfo> info(count);
     std::vector<int> kind(count);
     for (int i = 0; i < count; ++i)
@@ -559,6 +837,11 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
         for (int id : ids) {
             mixed |= info[id].k != k;
             kmax = std::max(kmax, info[id].k);
+        }
+        if (framing == 1) {
+            if (int rc = recover_bucket_dev(st, groups, info, ids, m, B, k, kmax, mixed, on_packet, cb_ctx)) return rc;
+            decoded += static_cast<int>(ids.size());
+            continue;
         }
         if (mixed) {  // m >= 2 (bucket key)
             // One var-k launch per chunk. Slot: blocks packed | rows packed | out [gn][emax][B] |
@@ -607,18 +890,16 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
             auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
                 const int g0 = start[c], gn = start[c + 1] - g0, total = first[c].back();
                 uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-                SG_CHECK(hipMemcpyAsync(d, h, static_cast<size_t>(total) * B, hipMemcpyHostToDevice, st.stream));
-                SG_CHECK(hipMemcpyAsync(d + o_rows, h + o_rows, total, hipMemcpyHostToDevice, st.stream));
-                SG_CHECK(hipMemcpyAsync(d + o_first, h + o_first, (gn + 1) * sizeof(int), hipMemcpyHostToDevice,
-                                        st.stream));
+                SG_CHECK(copy_h2d(d, h, static_cast<size_t>(total) * B, st.stream));
+                SG_CHECK(copy_h2d(d + o_rows, h + o_rows, total, st.stream));
+                SG_CHECK(copy_h2d(d + o_first, h + o_first, (gn + 1) * sizeof(int), st.stream));
                 const int rc = cauchy_256_decode_batch_out_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + o_first),
                                                                total, d, d + o_rows, d + o_out, d + o_orow,
                                                                reinterpret_cast<int *>(d + o_cnt), st.stream);
                 if (rc != 0) return rc;
                 count_launch(gn);
-                SG_CHECK(hipMemcpyAsync(h + o_out, d + o_out, gn * out_g, hipMemcpyDeviceToHost, st.stream));
-                SG_CHECK(hipMemcpyAsync(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax), hipMemcpyDeviceToHost,
-                                        st.stream));
+                SG_CHECK(copy_d2h(h + o_out, d + o_out, gn * out_g, st.stream));
+                SG_CHECK(copy_d2h(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
                 if (!on_packet) {
                     fin = [] {};
                     return 0;
@@ -638,7 +919,7 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
                 };
                 return 0;
             };
-            if (int rc = pipeline(st, chunks, slot_bytes, prepare, submit)) return rc;
+            if (int rc = pipeline(st, chunks, slot_bytes, slot_bytes, prepare, submit)) return rc;
             decoded += static_cast<int>(ids.size());
             continue;
         }
@@ -682,17 +963,15 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
         auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
             const int g0 = c * per, gn = std::min(per, n - g0);
             uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-            SG_CHECK(hipMemcpyAsync(d, h, gn * in_g, hipMemcpyHostToDevice, st.stream));
-            SG_CHECK(hipMemcpyAsync(d + o_rows, h + o_rows, gn * static_cast<size_t>(k), hipMemcpyHostToDevice,
-                                    st.stream));
+            SG_CHECK(copy_h2d(d, h, gn * in_g, st.stream));
+            SG_CHECK(copy_h2d(d + o_rows, h + o_rows, gn * static_cast<size_t>(k), st.stream));
             if (m >= 2) {
                 const int rc = cauchy_256_decode_batch_out(k, m, B, gn, d, d + o_rows, d + o_out, d + o_orow,
                                                            reinterpret_cast<int *>(d + o_cnt), st.stream);
                 if (rc != 0) return rc;
                 count_launch(gn);
-                SG_CHECK(hipMemcpyAsync(h + o_out, d + o_out, gn * out_g, hipMemcpyDeviceToHost, st.stream));
-                SG_CHECK(hipMemcpyAsync(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax),
-                                        hipMemcpyDeviceToHost, st.stream));
+                SG_CHECK(copy_d2h(h + o_out, d + o_out, gn * out_g, st.stream));
+                SG_CHECK(copy_d2h(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
             } else {
                 // m == 1 (cauchy_decode_m1): the one erasure lands in place in block k-1, the
                 // single recovery block (n_orig = k-1 originals precede it)
@@ -701,6 +980,7 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
                 count_launch(gn);
                 SG_CHECK(hipMemcpy2DAsync(h + o_out, B, d + static_cast<size_t>(k - 1) * B, in_g, B, gn,
                                           hipMemcpyDeviceToHost, st.stream));
+                g_d2h.fetch_add(static_cast<long long>(gn) * B, std::memory_order_relaxed);
             }
             if (!on_packet) {  // decode only (no delivery): still wait for the chunk before the
                 fin = [] {};   // slot is reused and before the call returns
@@ -730,7 +1010,7 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
             };
             return 0;
         };
-        if (int rc = pipeline(st, chunks, slot_bytes, prepare, submit)) return rc;
+        if (int rc = pipeline(st, chunks, slot_bytes, slot_bytes, prepare, submit)) return rc;
         decoded += n;
     }
     return decoded;
@@ -739,5 +1019,16 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
 extern "C" int shorthair_groups_stats(long long *launches, long long *groups) {
     if (launches) *launches = g_launches.load(std::memory_order_relaxed);
     if (groups) *groups = g_groups.load(std::memory_order_relaxed);
+    return 0;
+}
+
+extern "C" int shorthair_groups_set_framing(int where) {
+    if (where != 0 && where != 1) return -1;
+    return g_framing.exchange(where, std::memory_order_relaxed);
+}
+
+extern "C" int shorthair_groups_traffic(long long *h2d_bytes, long long *d2h_bytes) {
+    if (h2d_bytes) *h2d_bytes = g_h2d.load(std::memory_order_relaxed);
+    if (d2h_bytes) *d2h_bytes = g_d2h.load(std::memory_order_relaxed);
     return 0;
 }

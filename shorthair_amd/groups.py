@@ -34,6 +34,10 @@ lib.shorthair_encode_groups.argtypes = [_c.POINTER(TxGroup), _c.c_int]
 lib.shorthair_encode_groups.restype = _c.c_int
 lib.shorthair_recover_groups.argtypes = [_c.POINTER(RxGroup), _c.c_int, ON_PACKET, _c.c_void_p]
 lib.shorthair_recover_groups.restype = _c.c_int
+lib.shorthair_groups_set_framing.argtypes = [_c.c_int]
+lib.shorthair_groups_set_framing.restype = _c.c_int
+lib.shorthair_groups_traffic.argtypes = [_c.c_void_p, _c.c_void_p]
+lib.shorthair_groups_traffic.restype = _c.c_int
 
 
 def _bufs(items):
@@ -41,6 +45,22 @@ def _bufs(items):
     bufs = [_c.create_string_buffer(bytes(b), max(1, len(b))) for b in items]
     arr = (_c.c_void_p * max(1, len(bufs)))(*[_c.addressof(b) for b in bufs])
     return bufs, arr
+
+
+def set_framing(where):
+    """Where encode_groups / recover_groups frame payloads into blocks: 0 = host threads (default),
+    1 = the GPU. Returns the previous value; raises ValueError for anything else."""
+    prev = lib.shorthair_groups_set_framing(where)
+    if prev < 0:
+        raise ValueError("set_framing: 0 (host) or 1 (GPU)")
+    return prev
+
+
+def traffic():
+    """(h2d_bytes, d2h_bytes) the packet-group calls copied since the library was loaded."""
+    a, b = _c.c_longlong(0), _c.c_longlong(0)
+    lib.shorthair_groups_traffic(_c.byref(a), _c.byref(b))
+    return a.value, b.value
 
 
 def recovery_packet_bytes(k, lens):

@@ -93,6 +93,18 @@ int shorthair_groups_stats(long long *launches, long long *groups);
  * each shorthair_*_groups call. */
 int shorthair_groups_set_framing(int where);
 
+/* How shorthair_recover_groups brings the recovered payloads of its m >= 2 buckets back. 0 = the whole
+ * recovered blocks -- every slot up to min(k, m) per group, zero padding included -- cross PCIe and the
+ * host applies the length-prefix rule (the default). 1 = the GPU applies it (shorthair_unframe_batch,
+ * shorthair_unframe.h) and the copy has two phases: 5 bytes per slot and the payload total on the
+ * staging stream, then exactly the packed payload bytes on a second stream of the library's once the
+ * chunk has completed. Callbacks (group, id, bytes, order), return values, buckets, chunks and
+ * launches are the same either way, on both framing routes; m == 1 buckets and k == 1 groups are
+ * delivered as with 0. With on_packet == NULL the kernel and both copies still run.
+ * Returns the previous value, -1 for any other argument (nothing changes). Read once at the start of
+ * each shorthair_recover_groups call. */
+int shorthair_groups_set_delivery(int where);
+
 /* Cumulative bytes the two calls copied host->device and device->host since load. Either pointer may
  * be NULL. Returns 0. */
 int shorthair_groups_traffic(long long *h2d_bytes, long long *d2h_bytes);

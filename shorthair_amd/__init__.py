@@ -14,7 +14,8 @@ import os
 
 __all__ = ["lib", "Block", "CAUCHY_256_VERSION", "cauchy_256_init", "cauchy_256_encode",
            "cauchy_256_decode", "encode_batch", "decode_batch", "decode_batch_out",
-           "encode_batch_var", "decode_batch_out_var", "frame_batch", "groups_stats",
+           "encode_batch_var", "decode_batch_out_var", "frame_batch", "unframe_batch", "unframe_scratch_bytes",
+           "UNFRAME_TILE_SLOTS", "UNFRAME_SCAN_PASS", "groups_stats",
            "fill_synthetic", "erasure_pattern", "batch_reserve", "batch_errors", "has_fixed", "path", "default_stream", "sync", "LIB_PATH",
            "EXPORTED_SYMBOLS"]
 
@@ -35,8 +36,13 @@ EXPORTED_SYMBOLS = [
     "gf256_muladd_mem", "gf256_memswap",
     "shorthair_recovery_packet_bytes", "shorthair_encode_groups", "shorthair_recover_groups",
     "shorthair_groups_stats", "shorthair_groups_set_framing", "shorthair_groups_traffic",
-    "shorthair_frame_batch",
+    "shorthair_frame_batch", "shorthair_unframe_scratch_bytes", "shorthair_unframe_batch",
+    "shorthair_groups_set_delivery",
 ]
+
+# include/shorthair_unframe.h: slots per tile sum, and tile sums the scan workgroup takes per pass
+UNFRAME_TILE_SLOTS = 256
+UNFRAME_SCAN_PASS = 256
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} not built: run `python shorthair_amd/build.py` "
@@ -80,6 +86,11 @@ lib.cauchy_256_decode_batch_out_var.argtypes = [_c.c_int] * 4 + [_c.c_void_p, _c
 lib.cauchy_256_decode_batch_out_var.restype = _c.c_int
 lib.shorthair_frame_batch.argtypes = [_c.c_int, _c.c_int, _c.c_void_p, _c.c_longlong] + [_c.c_void_p] * 5
 lib.shorthair_frame_batch.restype = _c.c_int
+lib.shorthair_unframe_scratch_bytes.argtypes = [_c.c_int, _c.c_int]
+lib.shorthair_unframe_scratch_bytes.restype = _c.c_longlong
+lib.shorthair_unframe_batch.argtypes = ([_c.c_int] * 3 + [_c.c_longlong] + [_c.c_void_p] * 3 + [_c.c_longlong] +
+                                        [_c.c_void_p] * 4)
+lib.shorthair_unframe_batch.restype = _c.c_int
 lib.shorthair_groups_stats.argtypes = [_c.c_void_p, _c.c_void_p]
 lib.shorthair_groups_stats.restype = _c.c_int
 lib.cauchy_256_batch_reserve.argtypes = [_c.c_int] * 4
@@ -194,6 +205,31 @@ def frame_batch(block_bytes, total_blocks, payload, payload_bytes, off, length, 
         return t if t is None or isinstance(t, int) else int(t.data_ptr())
     return _check(lib.shorthair_frame_batch(block_bytes, total_blocks, ptr(payload), payload_bytes, ptr(off),
                                             ptr(length), ptr(raw), ptr(blocks), _stream(stream)), "frame_batch")
+
+
+def unframe_scratch_bytes(groups, emax):
+    """Bytes of device scratch unframe_batch needs for (groups, emax). Host only; raises ValueError on
+    invalid arguments."""
+    n = lib.shorthair_unframe_scratch_bytes(groups, emax)
+    if n < 0:
+        raise ValueError("unframe_scratch_bytes: bad arguments")
+    return n
+
+
+def unframe_batch(block_bytes, groups, emax, group_stride_blocks, out, out_count, payload, payload_capacity,
+                  off, length, scratch, stream=None):
+    """Unframe recovered blocks on the GPU (include/shorthair_unframe.h): slot s = g * emax + i reads the
+    block at out + (g * group_stride_blocks + i) * B; length[s] = its u16 prefix p, -2 (p > B - 2) or -1
+    (i >= out_count[g]); off[s] = the exclusive sum of max(length, 0), off[groups * emax] the total;
+    block bytes [2, 2 + p) are packed at payload + off[s]. out uint8 (8-byte aligned), out_count int32
+    [groups] or None, payload uint8 [payload_capacity], off int64 [groups * emax + 1], length int32
+    [groups * emax], scratch uint8 [unframe_scratch_bytes(groups, emax)]: cuda tensors, or integer device
+    addresses."""
+    def ptr(t):
+        return t if t is None or isinstance(t, int) else int(t.data_ptr())
+    return _check(lib.shorthair_unframe_batch(block_bytes, groups, emax, group_stride_blocks, ptr(out),
+                                              ptr(out_count), ptr(payload), payload_capacity, ptr(off),
+                                              ptr(length), ptr(scratch), _stream(stream)), "unframe_batch")
 
 
 def groups_stats():

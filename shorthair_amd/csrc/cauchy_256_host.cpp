@@ -23,11 +23,13 @@
 #include "../../include/cauchy_256.h"
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/shorthair_frame.h"
+#include "../../include/shorthair_unframe.h"
 #include "cauchy_math.hpp"
 #include "colsnip.h"
 #include "frame.hpp"
 #include "kernels.hpp"
 #include "measure.hpp"
+#include "unframe.hpp"
 
 namespace {
 
@@ -1126,6 +1128,39 @@ extern "C" int shorthair_frame_batch(int block_bytes, int total_blocks, const vo
     std::lock_guard<std::mutex> g(st->mu);
     SH_CHECK(sh::launch_frame(block_bytes, total_blocks, static_cast<const uint8_t *>(d_payload), payload_bytes,
                               d_off, d_len, d_raw, static_cast<uint8_t *>(d_blocks), st->d_errors, s));
+    return 0;
+}
+
+extern "C" long long shorthair_unframe_scratch_bytes(int groups, int emax) {
+    if (groups < 0 || emax < 1 || emax > 255) return -1;
+    const long long slots = static_cast<long long>(groups) * emax;
+    if (slots > 0x7fffffffll) return -1;
+    return sh::unframe_scratch_bytes(slots);
+}
+
+extern "C" int shorthair_unframe_batch(int block_bytes, int groups, int emax, long long group_stride_blocks,
+                                       const void *d_out, const int *d_out_count, void *d_payload,
+                                       long long payload_capacity, long long *d_off, int *d_len, void *d_scratch,
+                                       void *stream) {
+    if (block_bytes < 8 || block_bytes % 8 != 0 || groups < 0 || emax < 1 || emax > 255) return -1;
+    if (static_cast<long long>(groups) * emax > 0x7fffffffll) return -1;
+    if (group_stride_blocks < emax || payload_capacity < 0) return -1;
+    if (reinterpret_cast<uintptr_t>(d_out) % 8 != 0 || reinterpret_cast<uintptr_t>(d_off) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(d_len) % 4 != 0 || reinterpret_cast<uintptr_t>(d_scratch) % 8 != 0)
+        return -1;
+    if (groups > 0 && (!d_out || !d_off || !d_len || !d_scratch || (payload_capacity > 0 && !d_payload))) return -1;
+    if (groups == 0) return 0;
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    hipStream_t s = pick(stream);
+    StreamState *st = stream_state(c, s);
+    if (!st) return -2;
+    // under the stream's lock, like shorthair_frame_batch's count
+    std::lock_guard<std::mutex> g(st->mu);
+    SH_CHECK(sh::launch_unframe(block_bytes, groups, emax, group_stride_blocks, static_cast<const uint8_t *>(d_out),
+                                d_out_count, static_cast<uint8_t *>(d_payload), payload_capacity, d_off, d_len,
+                                d_scratch, st->d_errors, s));
     return 0;
 }
 

@@ -17,6 +17,10 @@
 // shorthair_groups_set_framing(1) moves the framing to the GPU ("Device framing" below): the host
 // threads then pack only the payload bytes into the pinned slot, shorthair_frame_batch builds the
 // blocks in device memory, and everything else -- buckets, chunks, codec calls, finishers -- is shared.
+//
+// shorthair_groups_set_delivery(1) moves the receiver's unframing to the GPU ("Device delivery" below):
+// shorthair_unframe_batch packs the recovered payloads of an m >= 2 chunk in device memory and only
+// they, their lengths and rows come back, in two copies; the callbacks are the same.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 #include <emmintrin.h>
@@ -36,6 +40,7 @@
 
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/shorthair_frame.h"
+#include "../../include/shorthair_unframe.h"
 #include "kernels.hpp"
 #include "measure.hpp"
 #include "../../include/shorthair_groups.h"
@@ -196,12 +201,14 @@ struct Slot {
     size_t nh = 0, nd = 0;
     hipEvent_t ev = nullptr;
     std::function<void()> finish;  // empty: nothing pending
+    std::function<void()> late;    // device delivery: set by finish, run once the next chunk is prepared
 };
 
 struct Staging {
     std::mutex mu;  // one packet-group call at a time (shared slots)
     bool ready = false;
     hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;  // device delivery: the second-phase D2H copies (created on first use)
     Slot slot[2];
 };
 
@@ -250,6 +257,13 @@ int drain(Slot &s) {
     return 0;
 }
 
+void run_late(Slot &s) {
+    if (!s.late) return;
+    auto f = std::move(s.late);
+    s.late = nullptr;
+    f();
+}
+
 // Run `chunks` chunks through the two slots: prepare(i, slot) frames chunk i into the slot's
 // pinned buffer, submit(i, slot) enqueues its copies and kernels and returns the finisher.
 template <class Prep, class Submit>
@@ -260,6 +274,7 @@ int pipeline(Staging &st, int chunks, size_t slot_h, size_t slot_d, Prep prepare
         if ((err = drain(s))) break;
         if ((err = ensure_slot(s, slot_h, slot_d))) break;
         prepare(i, s);
+        run_late(s);  // (the slot's previous chunk: its second-phase copy ran beside prepare)
         std::function<void()> fin;
         if ((err = submit(i, s, fin))) break;
         if (hipEventRecord(s.ev, st.stream) != hipSuccess) {
@@ -271,9 +286,13 @@ int pipeline(Staging &st, int chunks, size_t slot_h, size_t slot_d, Prep prepare
     for (Slot &s : st.slot) {
         if (err) {
             (void)hipStreamSynchronize(st.stream);
+            if (st.stream2) (void)hipStreamSynchronize(st.stream2);
             s.finish = nullptr;
+            s.late = nullptr;
         } else if (int e = drain(s)) {
             err = e;
+        } else {
+            run_late(s);
         }
     }
     return err;
@@ -299,6 +318,10 @@ hipError_t copy_d2h(void *dst, const void *src, size_t n, hipStream_t stream) {
 
 // shorthair_groups_set_framing: 0 = host threads frame the blocks, 1 = the GPU does.
 std::atomic<int> g_framing{0};
+
+// shorthair_groups_set_delivery: 0 = whole recovered blocks come back and the host unframes them,
+// 1 = the GPU unframes them and only the packed payloads come back.
+std::atomic<int> g_delivery{0};
 
 // Bucket key of a group: the K of the compiled kernel that codes (k, m, B), or k itself.
 int bucket_k(int k, int m, int B) {
@@ -675,11 +698,98 @@ int rx_info(const ShorthairRxGroup &g, RxInfo &r) {
     return 1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Device delivery (shorthair_groups_set_delivery(1)), every m >= 2 bucket on both framing routes. After
+// the decode call shorthair_unframe_batch packs the chunk's delivered payloads in a device-only region
+// behind the slot's delivery-0 layout, and the D2H copy has two phases, as the host cannot know the
+// payload total before the decode:
+//   device region: payload[slots * min(B - 2, 65535)] | off[slots + 1] | len[slots] | scratch
+//   pinned region: total (8 B) | len[slots] (4 B each) | rows[slots] | pad to 16 | the packed payloads
+//   1. on the staging stream: len[], the decode's out rows and off[slots] (the total);
+//   2. in the finisher, after the slot's event: `total` packed bytes on Staging::stream2 -- nothing
+//      else is pending on the device for that region, and the staging stream keeps running the next
+//      chunk. The wait for that copy and the on_packet calls from the pinned packed buffer, in
+//      delivery 0's order, are the slot's `late` step: the pipeline runs it once the host threads have
+//      framed the slot's next chunk (which touches neither region), before that chunk is submitted.
+// ---------------------------------------------------------------------------------------------
+struct D1Layout {
+    size_t cap;                        // bytes of the packed-payload buffers
+    size_t d_off, d_len, d_scr, d_end;  // device region (the payload at 0)
+    size_t h_len, h_rows, h_pay, h_end;  // pinned region (the total at 0)
+};
+D1Layout d1_layout(size_t gn, int emax, int B) {
+    const size_t slots = gn * emax;
+    D1Layout L;
+    L.cap = slots * static_cast<size_t>(std::min(B - 2, 65535));
+    L.d_off = up16(L.cap);
+    L.d_len = L.d_off + 8 * (slots + 1);
+    L.d_scr = up16(L.d_len + 4 * slots);
+    L.d_end = L.d_scr + static_cast<size_t>(shorthair_unframe_scratch_bytes(static_cast<int>(gn), emax));
+    L.h_len = 16;
+    L.h_rows = L.h_len + 4 * slots;
+    L.h_pay = up16(L.h_rows + slots);
+    L.h_end = L.h_pay + L.cap;
+    return L;
+}
+
+// The delivery-1 tail of a chunk of gn groups (chunk-local group j = ids[g0 + j]) whose decode call has
+// been enqueued: d_out [gn][emax][B], d_orow [gn][emax], d_cnt [gn] in device memory; the regions
+// start d_base / h_base bytes into the slot. A failure in the finisher lands in *err.
+int deliver1_tail(Staging &st, Slot &s, size_t d_base, size_t h_base, int B, int gn, int emax,
+                  const uint8_t *d_out, const uint8_t *d_orow, const int *d_cnt,
+                  const ShorthairRxGroup *groups, const std::vector<RxInfo> &info, const std::vector<int> &ids,
+                  int g0, shorthair_on_packet_fn on_packet, void *cb_ctx, int *err, std::function<void()> &fin) {
+    const D1Layout L = d1_layout(gn, emax, B);
+    const size_t slots = static_cast<size_t>(gn) * emax;
+    uint8_t *h = static_cast<uint8_t *>(s.h) + h_base, *d = static_cast<uint8_t *>(s.d) + d_base;
+    if (!st.stream2) SG_CHECK(hipStreamCreateWithFlags(&st.stream2, hipStreamNonBlocking));
+    const int rc = shorthair_unframe_batch(B, gn, emax, emax, d_out, d_cnt, d, static_cast<long long>(L.cap),
+                                           reinterpret_cast<long long *>(d + L.d_off),
+                                           reinterpret_cast<int *>(d + L.d_len), d + L.d_scr, st.stream);
+    if (rc != 0) return rc;
+    SG_CHECK(copy_d2h(h, d + L.d_off + 8 * slots, 8, st.stream));
+    SG_CHECK(copy_d2h(h + L.h_len, d + L.d_len, 4 * slots, st.stream));
+    SG_CHECK(copy_d2h(h + L.h_rows, d_orow, slots, st.stream));
+    hipStream_t second = st.stream2;
+    fin = [=, &s, &info, &ids]() {
+        long long total;
+        std::memcpy(&total, h, 8);
+        if (total < 0 || static_cast<unsigned long long>(total) > L.cap) {
+            *err = -2;
+            return;
+        }
+        if (total > 0 && copy_d2h(h + L.h_pay, d, static_cast<size_t>(total), second) != hipSuccess) {
+            *err = -2;
+            return;
+        }
+        s.late = [=, &info, &ids]() {
+            if (hipStreamSynchronize(second) != hipSuccess) {
+                *err = -2;
+                return;
+            }
+            if (!on_packet) return;
+            const int *len = reinterpret_cast<const int *>(h + L.h_len);
+            const uint8_t *pay = h + L.h_pay;
+            for (int j = 0; j < gn; ++j) {  // RecoverGroup :741-756; the prefix rule was applied on the GPU
+                const int gi = ids[g0 + j];
+                const int e = info[gi].k - groups[gi].n_orig;
+                for (int i = 0; i < emax; ++i) {
+                    const int l = len[static_cast<size_t>(j) * emax + i];
+                    if (l < 0) continue;
+                    if (i < e) on_packet(cb_ctx, gi, h[L.h_rows + static_cast<size_t>(j) * emax + i], pay, l);
+                    pay += l;
+                }
+            }
+        };
+    };
+    return 0;
+}
+
 // Device framing, receiver (layout above): originals as payload bytes, the recovery packets' bodies
 // as raw blocks.
 int recover_bucket_dev(Staging &st, const ShorthairRxGroup *groups, const std::vector<RxInfo> &info,
                        const std::vector<int> &ids, int m, int B, int k, int kmax, bool mixed,
-                       shorthair_on_packet_fn on_packet, void *cb_ctx) {
+                       shorthair_on_packet_fn on_packet, void *cb_ctx, bool d1, int *d1_err) {
     const int n = static_cast<int>(ids.size());
     const int emax = std::min(mixed ? kmax : k, m);
     const size_t out_g = m >= 2 ? static_cast<size_t>(emax) * B : static_cast<size_t>(B);
@@ -706,6 +816,13 @@ int recover_bucket_dev(Staging &st, const ShorthairRxGroup *groups, const std::v
         const size_t outs = ch.gn(c) * out_g + static_cast<size_t>(ch.gn(c)) * emax;
         nh = std::max(nh, head + outs);
         nd = std::max(nd, head + static_cast<size_t>(ch.nb(c)) * B + outs + 4 + ch.gn(c) * sizeof(int));
+    }
+    const size_t h_d1 = up16(nh), d_d1 = up16(nd);  // device delivery: its regions behind the layout above
+    if (d1 && m >= 2) {
+        size_t max_gn = 0;
+        for (int c = 0; c < ch.chunks(); ++c) max_gn = std::max<size_t>(max_gn, ch.gn(c));
+        nh = h_d1 + d1_layout(max_gn, emax, B).h_end;
+        nd = d_d1 + d1_layout(max_gn, emax, B).d_end;
     }
     auto prepare = [&](int c, Slot &s) {
         const int g0 = ch.g0(c), gn = ch.gn(c);
@@ -761,6 +878,10 @@ int recover_bucket_dev(Staging &st, const ShorthairRxGroup *groups, const std::v
                                                      reinterpret_cast<int *>(d + o_cnt), st.stream);
             if (rc != 0) return rc;
             count_launch(gn);
+            if (d1)
+                return deliver1_tail(st, s, d_d1, h_d1, B, gn, emax, d + o_out, d + o_orow,
+                                     reinterpret_cast<const int *>(d + o_cnt), groups, info, ids, g0, on_packet,
+                                     cb_ctx, d1_err, fin);
             SG_CHECK(copy_d2h(h + h_out, d + o_out, gn * out_g, st.stream));
             SG_CHECK(copy_d2h(h + h_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
         } else {
@@ -808,6 +929,8 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
                                         shorthair_on_packet_fn on_packet, void *cb_ctx) {
     if (count < 0 || (count > 0 && !groups)) return -1;
     const int framing = g_framing.load(std::memory_order_relaxed);
+    const int delivery = g_delivery.load(std::memory_order_relaxed);
+    int d1_err = 0;  // a failure in a delivery-1 finisher
     std::vector<RxInfo> info(count);
     std::vector<int> kind(count);
     for (int i = 0; i < count; ++i)
@@ -839,7 +962,10 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
             kmax = std::max(kmax, info[id].k);
         }
         if (framing == 1) {
-            if (int rc = recover_bucket_dev(st, groups, info, ids, m, B, k, kmax, mixed, on_packet, cb_ctx)) return rc;
+            if (int rc = recover_bucket_dev(st, groups, info, ids, m, B, k, kmax, mixed, on_packet, cb_ctx,
+                                            delivery == 1 && m >= 2, &d1_err))
+                return rc;
+            if (d1_err) return d1_err;
             decoded += static_cast<int>(ids.size());
             continue;
         }
@@ -863,6 +989,10 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
             const size_t o_orow = o_out + max_gn * out_g, o_cnt = (o_orow + max_gn * emax + 3) & ~size_t(3);
             const size_t o_first = o_cnt + max_gn * sizeof(int);
             const size_t slot_bytes = o_first + (max_gn + 1) * sizeof(int);
+            const bool d1 = delivery == 1;
+            const size_t base_d1 = up16(slot_bytes);  // device delivery: its regions behind the layout above
+            const size_t slot_h = d1 ? base_d1 + d1_layout(max_gn, emax, B).h_end : slot_bytes;
+            const size_t slot_d = d1 ? base_d1 + d1_layout(max_gn, emax, B).d_end : slot_bytes;
             auto prepare = [&](int c, Slot &s) {
                 const int g0 = start[c], gn = start[c + 1] - g0;
                 uint8_t *h = static_cast<uint8_t *>(s.h);
@@ -898,6 +1028,10 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
                                                                reinterpret_cast<int *>(d + o_cnt), st.stream);
                 if (rc != 0) return rc;
                 count_launch(gn);
+                if (d1)
+                    return deliver1_tail(st, s, base_d1, base_d1, B, gn, emax, d + o_out, d + o_orow,
+                                         reinterpret_cast<const int *>(d + o_cnt), groups, info, ids, g0, on_packet,
+                                         cb_ctx, &d1_err, fin);
                 SG_CHECK(copy_d2h(h + o_out, d + o_out, gn * out_g, st.stream));
                 SG_CHECK(copy_d2h(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
                 if (!on_packet) {
@@ -919,7 +1053,8 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
                 };
                 return 0;
             };
-            if (int rc = pipeline(st, chunks, slot_bytes, slot_bytes, prepare, submit)) return rc;
+            if (int rc = pipeline(st, chunks, slot_h, slot_d, prepare, submit)) return rc;
+            if (d1_err) return d1_err;
             decoded += static_cast<int>(ids.size());
             continue;
         }
@@ -934,8 +1069,13 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
         const int cap = std::min(per, n);
         const size_t slot_bytes = static_cast<size_t>(cap) * per_g + 64;
         // slot layout (chunk of gn groups, offsets for cap groups): blocks | rows | out | out rows | count
-        const size_t o_rows = cap * in_g, o_out = o_rows + cap * static_cast<size_t>(k);
+        // (device delivery reads d_out in 8-byte words: aligned then, within the 64 bytes of slack)
+        const bool d1 = delivery == 1 && m >= 2;
+        const size_t o_rows = cap * in_g, o_out = d1 ? up16(o_rows + cap * static_cast<size_t>(k)) : o_rows + cap * static_cast<size_t>(k);
         const size_t o_orow = o_out + cap * out_g, o_cnt = (o_orow + cap * static_cast<size_t>(emax) + 3) & ~size_t(3);
+        const size_t base_d1 = up16(slot_bytes);  // device delivery: its regions behind the layout above
+        const size_t slot_h = d1 ? base_d1 + d1_layout(cap, emax, B).h_end : slot_bytes;
+        const size_t slot_d = d1 ? base_d1 + d1_layout(cap, emax, B).d_end : slot_bytes;
         auto prepare = [&](int c, Slot &s) {
             const int g0 = c * per, gn = std::min(per, n - g0);
             uint8_t *h = static_cast<uint8_t *>(s.h);
@@ -970,6 +1110,10 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
                                                            reinterpret_cast<int *>(d + o_cnt), st.stream);
                 if (rc != 0) return rc;
                 count_launch(gn);
+                if (d1)
+                    return deliver1_tail(st, s, base_d1, base_d1, B, gn, emax, d + o_out, d + o_orow,
+                                         reinterpret_cast<const int *>(d + o_cnt), groups, info, ids, g0, on_packet,
+                                         cb_ctx, &d1_err, fin);
                 SG_CHECK(copy_d2h(h + o_out, d + o_out, gn * out_g, st.stream));
                 SG_CHECK(copy_d2h(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
             } else {
@@ -1010,7 +1154,8 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
             };
             return 0;
         };
-        if (int rc = pipeline(st, chunks, slot_bytes, slot_bytes, prepare, submit)) return rc;
+        if (int rc = pipeline(st, chunks, slot_h, slot_d, prepare, submit)) return rc;
+        if (d1_err) return d1_err;
         decoded += n;
     }
     return decoded;
@@ -1025,6 +1170,11 @@ extern "C" int shorthair_groups_stats(long long *launches, long long *groups) {
 extern "C" int shorthair_groups_set_framing(int where) {
     if (where != 0 && where != 1) return -1;
     return g_framing.exchange(where, std::memory_order_relaxed);
+}
+
+extern "C" int shorthair_groups_set_delivery(int where) {
+    if (where != 0 && where != 1) return -1;
+    return g_delivery.exchange(where, std::memory_order_relaxed);
 }
 
 extern "C" int shorthair_groups_traffic(long long *h2d_bytes, long long *d2h_bytes) {

@@ -36,6 +36,8 @@ lib.shorthair_recover_groups.argtypes = [_c.POINTER(RxGroup), _c.c_int, ON_PACKE
 lib.shorthair_recover_groups.restype = _c.c_int
 lib.shorthair_groups_set_framing.argtypes = [_c.c_int]
 lib.shorthair_groups_set_framing.restype = _c.c_int
+lib.shorthair_groups_set_delivery.argtypes = [_c.c_int]
+lib.shorthair_groups_set_delivery.restype = _c.c_int
 lib.shorthair_groups_traffic.argtypes = [_c.c_void_p, _c.c_void_p]
 lib.shorthair_groups_traffic.restype = _c.c_int
 
@@ -53,6 +55,16 @@ def set_framing(where):
     prev = lib.shorthair_groups_set_framing(where)
     if prev < 0:
         raise ValueError("set_framing: 0 (host) or 1 (GPU)")
+    return prev
+
+
+def set_delivery(where):
+    """How recover_groups brings recovered payloads back (m >= 2 buckets): 0 = whole blocks, unframed on
+    the host (default), 1 = unframed on the GPU, only the packed payloads cross PCIe. Returns the
+    previous value; raises ValueError for anything else."""
+    prev = lib.shorthair_groups_set_delivery(where)
+    if prev < 0:
+        raise ValueError("set_delivery: 0 (host) or 1 (GPU)")
     return prev
 
 

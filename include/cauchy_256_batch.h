@@ -41,6 +41,11 @@ int cauchy_256_decode_batch(int k, int m, int block_bytes, int groups, void *d_b
  * d_out[g][0 .. e_g-1][block_bytes] (dense, emax = min(k, m) slots per group) in the order the
  * in-place call would write them (i-th recovery block in array order <- i-th smallest erasure);
  * d_out_rows[g][i] receives that erasure index and d_out_count[g] = e_g. m >= 2 only.
+ * The unused slots are left untouched: no byte of d_out[g][e_g .. emax) or d_out_rows[g][e_g .. emax)
+ * is written, for a group with e_g = 0 and for one flagged d_out_count[g] = -1 (below) the whole of
+ * its emax slots, and nothing outside [groups][emax][block_bytes], [groups][emax] and [groups] is.
+ * d_blocks, d_rows, d_out and d_out_rows take any address; d_out_count is an int array and must be
+ * 4-byte aligned.
  */
 int cauchy_256_decode_batch_out(int k, int m, int block_bytes, int groups, const void *d_blocks,
                                 const unsigned char *d_rows, void *d_out, unsigned char *d_out_rows,
@@ -59,6 +64,9 @@ int cauchy_256_decode_batch_out(int k, int m, int block_bytes, int groups, const
  * Per-group semantics and bytes are those of cauchy_256_encode(k_g, m, ..) / cauchy_256_decode(k_g,
  * m, ..). The kernels are those cauchy_256_batch_path(kmax, m, block_bytes) reports, coding every
  * k_g <= kmax (the generator's column x is the same for every k).
+ * As in the uniform call, out[g][e_g .. emax) and out_rows[g][e_g .. emax) are left untouched (all
+ * emax slots of a group with e_g = 0 or d_out_count[g] = -1). d_first and d_out_count are int arrays
+ * and must be 4-byte aligned; every other pointer takes any address.
  * Host-checked (-1, nothing enqueued): kmax in 2..255, kmax + m <= 256, block_bytes % 8 == 0,
  * groups >= 0, 0 <= total_blocks <= groups * kmax, m >= 1 (encode) / m >= 2 (decode).
  * Malformed groups -- k_g outside 2..kmax, or a span that leaves [0, total_blocks] -- are seen only

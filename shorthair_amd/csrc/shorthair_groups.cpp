@@ -14,13 +14,17 @@
 // outputs are unframed on the host threads. So host framing, PCIe and kernels overlap, and the
 // only host work per byte is the framing copy the reference also does (its memset/memcpy).
 //
-// shorthair_groups_set_framing(1) moves the framing to the GPU ("Device framing" below): the host
-// threads then pack only the payload bytes into the pinned slot, shorthair_frame_batch builds the
-// blocks in device memory, and everything else -- buckets, chunks, codec calls, finishers -- is shared.
+// shorthair_groups_set_framing(1) moves the framing to the GPU: the host threads then pack only the
+// payload bytes into the pinned slot and shorthair_frame_batch builds the blocks in device memory.
 //
 // shorthair_groups_set_delivery(1) moves the receiver's unframing to the GPU ("Device delivery" below):
 // shorthair_unframe_batch packs the recovered payloads of an m >= 2 chunk in device memory and only
 // they, their lengths and rows come back, in two copies; the callbacks are the same.
+//
+// There is one copy of each thing for all routes: one chunk plan (Chunks), one slot layout per chunk
+// (slot_layout), one encode_bucket and one recover_bucket. The framing route decides only what
+// prepare writes into the pinned slot (put_block) and what is enqueued before the codec call
+// (submit_inputs); uniform or mixed k decides only which codec call runs and whether first[] exists.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 #include <emmintrin.h>
@@ -200,8 +204,8 @@ struct Slot {
     void *h = nullptr, *d = nullptr;
     size_t nh = 0, nd = 0;
     hipEvent_t ev = nullptr;
-    std::function<void()> finish;  // empty: nothing pending
-    std::function<void()> late;    // device delivery: set by finish, run once the next chunk is prepared
+    std::function<int()> finish;  // empty: nothing pending; returns 0 or the call's error
+    std::function<int()> late;    // device delivery: set by finish, run once the next chunk is prepared
 };
 
 struct Staging {
@@ -253,19 +257,20 @@ int drain(Slot &s) {
     SG_CHECK(hipEventSynchronize(s.ev));
     auto f = std::move(s.finish);
     s.finish = nullptr;
-    f();
-    return 0;
+    return f();
 }
 
-void run_late(Slot &s) {
-    if (!s.late) return;
+int run_late(Slot &s) {
+    if (!s.late) return 0;
     auto f = std::move(s.late);
     s.late = nullptr;
-    f();
+    return f();
 }
 
 // Run `chunks` chunks through the two slots: prepare(i, slot) frames chunk i into the slot's
-// pinned buffer, submit(i, slot) enqueues its copies and kernels and returns the finisher.
+// pinned buffer, submit(i, slot) enqueues its copies and kernels and returns the finisher. The
+// first error -- of a call, a copy or a finisher -- ends the run: both streams are waited for and
+// the finishers still pending are dropped.
 template <class Prep, class Submit>
 int pipeline(Staging &st, int chunks, size_t slot_h, size_t slot_d, Prep prepare, Submit submit) {
     int err = 0;
@@ -274,8 +279,8 @@ int pipeline(Staging &st, int chunks, size_t slot_h, size_t slot_d, Prep prepare
         if ((err = drain(s))) break;
         if ((err = ensure_slot(s, slot_h, slot_d))) break;
         prepare(i, s);
-        run_late(s);  // (the slot's previous chunk: its second-phase copy ran beside prepare)
-        std::function<void()> fin;
+        if ((err = run_late(s))) break;  // (the slot's previous chunk: its second-phase copy ran beside prepare)
+        std::function<int()> fin;
         if ((err = submit(i, s, fin))) break;
         if (hipEventRecord(s.ev, st.stream) != hipSuccess) {
             err = -2;
@@ -284,16 +289,13 @@ int pipeline(Staging &st, int chunks, size_t slot_h, size_t slot_d, Prep prepare
         s.finish = std::move(fin);
     }
     for (Slot &s : st.slot) {
-        if (err) {
-            (void)hipStreamSynchronize(st.stream);
-            if (st.stream2) (void)hipStreamSynchronize(st.stream2);
-            s.finish = nullptr;
-            s.late = nullptr;
-        } else if (int e = drain(s)) {
-            err = e;
-        } else {
-            run_late(s);
-        }
+        if (!err) err = drain(s);
+        if (!err) err = run_late(s);
+    }
+    if (err) {
+        (void)hipStreamSynchronize(st.stream);
+        if (st.stream2) (void)hipStreamSynchronize(st.stream2);
+        for (Slot &s : st.slot) s.finish = s.late = nullptr;
     }
     return err;
 }
@@ -314,6 +316,12 @@ hipError_t copy_h2d(void *dst, const void *src, size_t n, hipStream_t stream) {
 hipError_t copy_d2h(void *dst, const void *src, size_t n, hipStream_t stream) {
     g_d2h.fetch_add(static_cast<long long>(n), std::memory_order_relaxed);
     return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, stream);
+}
+// `height` rows of `width` bytes, spitch apart on the device, dpitch apart on the host
+hipError_t copy_d2h_2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height,
+                       hipStream_t stream) {
+    g_d2h.fetch_add(static_cast<long long>(width * height), std::memory_order_relaxed);
+    return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToHost, stream);
 }
 
 // shorthair_groups_set_framing: 0 = host threads frame the blocks, 1 = the GPU does.
@@ -346,6 +354,216 @@ std::vector<int> var_chunks(const std::vector<int> &ids, const std::function<int
     start.push_back(static_cast<int>(ids.size()));
     return start;
 }
+std::vector<int> uniform_chunks(int n, int per) {
+    std::vector<int> start;
+    for (int g = 0; g < n; g += per) start.push_back(g);
+    start.push_back(n);
+    return start;
+}
+
+// The k of a bucket's first group, the largest k in it, and whether its groups differ in k.
+struct BucketK {
+    int k, kmax;
+    bool mixed;
+};
+template <class Info>
+BucketK bucket_ks(const std::vector<Info> &info, const std::vector<int> &ids) {
+    BucketK b{info[ids[0]].k, info[ids[0]].k, false};
+    for (int id : ids) {
+        b.mixed |= info[id].k != b.k;
+        b.kmax = std::max(b.kmax, info[id].k);
+    }
+    return b;
+}
+
+// The chunk plan of a bucket, on every route. Chunk c is groups [start[c], start[c + 1]) of `ids`;
+// blk0[j] / pay0[j] are the first block and the first payload byte of group j counted from the
+// bucket's start (a group's payload bytes: what the device-framing route packs for it).
+struct Chunks {
+    std::vector<int> start;
+    std::vector<long long> blk0, pay0;
+    int chunks() const { return static_cast<int>(start.size()) - 1; }
+    int g0(int c) const { return start[c]; }
+    int gn(int c) const { return start[c + 1] - start[c]; }
+    int nb(int c) const { return static_cast<int>(blk0[start[c + 1]] - blk0[start[c]]); }
+    size_t pay(int c) const { return static_cast<size_t>(pay0[start[c + 1]] - pay0[start[c]]); }
+    // group j of chunk c, counted from the chunk's start (j == gn(c): the chunk's end)
+    long long blk(int c, int j) const { return blk0[start[c] + j] - blk0[start[c]]; }
+    long long payoff(int c, int j) const { return pay0[start[c] + j] - pay0[start[c]]; }
+    void put_first(int c, int *first) const {  // first[gn + 1] of the var-k codec calls
+        for (int j = 0; j <= gn(c); ++j) first[j] = static_cast<int>(blk(c, j));
+    }
+};
+// A uniform bucket is cut every chunk_bytes() / per_group groups, a mixed one by var_chunks with
+// var_extra bytes per group; k_of(id) and pay_of(id) give a group's blocks and payload bytes
+// (pay_of empty on the host-framing route, which has no use for pay0).
+Chunks plan_chunks(const std::vector<int> &ids, bool mixed, int B, size_t per_group, size_t var_extra,
+                   const std::function<int(int)> &k_of, const std::function<long long(int)> &pay_of) {
+    const int n = static_cast<int>(ids.size());
+    Chunks ch;
+    ch.start = mixed ? var_chunks(ids, k_of, B, var_extra)
+                     : uniform_chunks(n, static_cast<int>(std::max<size_t>(1, chunk_bytes() / per_group)));
+    ch.blk0.assign(n + 1, 0);
+    ch.pay0.assign(n + 1, 0);
+    for (int j = 0; j < n; ++j) {
+        ch.blk0[j + 1] = ch.blk0[j] + k_of(ids[j]);
+        if (pay_of) ch.pay0[j + 1] = ch.pay0[j] + pay_of(ids[j]);
+    }
+    return ch;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device delivery (shorthair_groups_set_delivery(1)), every m >= 2 bucket on both framing routes. After
+// the decode call shorthair_unframe_batch packs the chunk's delivered payloads in a device-only region
+// behind the slot's delivery-0 layout, and the D2H copy has two phases, as the host cannot know the
+// payload total before the decode:
+//   device region: payload[slots * min(B - 2, 65535)] | off[slots + 1] | len[slots] | scratch
+//   pinned region: total (8 B) | len[slots] (4 B each) | rows[slots] | pad to 16 | the packed payloads
+//   1. on the staging stream: len[], the decode's out rows and off[slots] (the total);
+//   2. in the finisher, after the slot's event: `total` packed bytes on Staging::stream2 -- nothing
+//      else is pending on the device for that region, and the staging stream keeps running the next
+//      chunk. The wait for that copy and the on_packet calls from the pinned packed buffer, in
+//      delivery 0's order, are the slot's `late` step: the pipeline runs it once the host threads have
+//      framed the slot's next chunk (which touches neither region), before that chunk is submitted.
+// ---------------------------------------------------------------------------------------------
+inline size_t up16(size_t x) { return (x + 15) & ~size_t(15); }
+struct D1Layout {
+    size_t cap;                        // bytes of the packed-payload buffers
+    size_t d_off, d_len, d_scr, d_end;  // device region (the payload at 0)
+    size_t h_len, h_rows, h_pay, h_end;  // pinned region (the total at 0)
+};
+D1Layout d1_layout(size_t gn, int emax, int B) {
+    const size_t slots = gn * emax;
+    D1Layout L;
+    L.cap = slots * static_cast<size_t>(std::min(B - 2, 65535));
+    L.d_off = up16(L.cap);
+    L.d_len = L.d_off + 8 * (slots + 1);
+    L.d_scr = up16(L.d_len + 4 * slots);
+    L.d_end = L.d_scr + static_cast<size_t>(shorthair_unframe_scratch_bytes(static_cast<int>(gn), emax));
+    L.h_len = 16;
+    L.h_rows = L.h_len + 4 * slots;
+    L.h_pay = up16(L.h_rows + slots);
+    L.h_end = L.h_pay + L.cap;
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The slot layout of one chunk: nb blocks in gn groups, `pay` payload bytes. One rule on every route:
+// blocks and out are 16-byte aligned, count is 4-byte aligned, the delivery-1 regions are 16-byte
+// aligned; route 0's rows and first[], copies of their own, start 16-byte aligned as well.
+//
+// Host framing (route 0): the pinned slot mirrors the device slot, and blocks, rows (receiver) and
+// first[] (mixed-k buckets) go over in a copy each:
+//   blocks[nb][B] | pad to 16 | rows[nb] | pad to 16 | first[gn + 1] (4 B each) | pad to 16 | outputs
+// Device framing (route 1): the pinned slot carries only what the GPU cannot know, back to back, and
+// goes over in one copy of h2d bytes; shorthair_frame_batch builds the blocks behind it:
+//   off[nb] (8 B each) | len[nb] (4 B) | first[gn + 1] | rows[nb] | raw[nb] (receiver) | pad to 16 |
+//   the payload bytes packed (recovery bodies among them, raw = 1) | pad to 16 | blocks[nb][B]
+//   (device only) | pad to 16 | outputs; on the pinned side the outputs follow the copy, at up16(h2d).
+// Outputs, sender: out[gn][m][B]. Receiver: out[gn][emax][B] (m == 1: [gn][B], pinned side only) |
+// out rows[gn][emax] | pad to 4 | count[gn] (device only). The delivery-1 regions (d1_layout) do not
+// follow the chunk's own end but the largest end among the bucket's chunks (slot_bytes), 16-byte
+// aligned: a chunk's pinned region is still read by its `late` step after the slot's next chunk has
+// been prepared, so no chunk's inputs or outputs may reach it.
+// ---------------------------------------------------------------------------------------------
+struct SlotLayout {
+    size_t off, len, first, rows, raw, pay, h2d;  // inputs (off, len, raw, pay, h2d: route 1 only)
+    size_t blk, out, orow, cnt;                    // device side
+    size_t h_out, h_orow;                          // pinned side
+    size_t out_g;                                  // out bytes per group
+    size_t h_end, d_end;                           // 16-byte aligned ends of all of the above
+    size_t h_d1n, d_d1n;                           // bytes of the chunk's delivery-1 regions (0 without)
+};
+SlotLayout slot_layout(bool rx, int framing, bool mixed, size_t nb, size_t gn, size_t pay, int m, int emax,
+                       int B, bool d1) {
+    const size_t F = mixed ? 4 * (gn + 1) : 0, R = rx ? nb : 0, orows = rx ? gn * emax : 0;
+    SlotLayout L{};
+    L.out_g = static_cast<size_t>(rx ? (m >= 2 ? emax : 1) : m) * B;
+    if (framing == 1) {
+        L.len = 8 * nb;
+        L.first = L.len + 4 * nb;
+        L.rows = L.first + F;
+        L.raw = L.rows + R;
+        L.pay = up16(L.raw + R);
+        L.h2d = L.pay + pay;
+        L.blk = up16(L.h2d);
+        L.out = up16(L.blk + nb * B);
+        L.h_out = up16(L.h2d);
+    } else {
+        L.rows = up16(nb * B);
+        L.first = up16(L.rows + R);
+        L.out = L.h_out = up16(L.first + F);
+    }
+    L.orow = L.out + gn * L.out_g;
+    L.h_orow = L.h_out + gn * L.out_g;
+    L.cnt = (L.orow + orows + 3) & ~size_t(3);
+    L.d_end = up16(L.cnt + (rx ? 4 * gn : 0));
+    L.h_end = up16(L.h_orow + orows);
+    L.d_d1n = d1 ? d1_layout(gn, emax, B).d_end : 0;
+    L.h_d1n = d1 ? d1_layout(gn, emax, B).h_end : 0;
+    return L;
+}
+
+// Block x of a chunk into the pinned slot; its payload starts p bytes into the chunk's payload bytes.
+// Route 0 frames it as the reference does, "[len u16 LE][payload][zeros up to B]" (EncodeQueued
+// :540-557, RecoverGroup :710-725), or copies a recovery packet's block verbatim (raw, len == B:
+// :727-735). Route 1 packs the bytes alone and notes off and len: the GPU frames them.
+inline void put_block(int framing, uint8_t *h, const SlotLayout &L, int B, long long x, long long p,
+                      const void *src, int len, bool raw) {
+    const uint8_t *from = static_cast<const uint8_t *>(src);
+    if (framing == 1) {
+        reinterpret_cast<long long *>(h + L.off)[x] = p;
+        reinterpret_cast<int *>(h + L.len)[x] = len;
+        framing_copy(h + L.pay + p, from, len);
+        return;
+    }
+    uint8_t *blk = h + L.blk + static_cast<size_t>(x) * B;
+    if (raw) {
+        framing_copy(blk, from, B);
+        return;
+    }
+    put_u16(blk, len);
+    framing_copy(blk + 2, from, len);
+    std::memset(blk + 2 + len, 0, B - 2 - len);
+}
+
+// What a chunk's codec call reads, from the pinned slot prepare() filled to the device slot: route 0
+// copies blocks, rows and first[]; route 1 copies the head and frames the blocks on the GPU.
+int submit_inputs(Staging &st, Slot &s, int framing, const SlotLayout &L, bool rx, bool mixed, int nb, int gn,
+                  size_t pay, int B) {
+    uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
+    if (framing == 1) {
+        SG_CHECK(copy_h2d(d, h, L.h2d, st.stream));
+        return shorthair_frame_batch(B, nb, d + L.pay, static_cast<long long>(pay),
+                                     reinterpret_cast<const long long *>(d + L.off),
+                                     reinterpret_cast<const int *>(d + L.len), rx ? d + L.raw : nullptr, d + L.blk,
+                                     st.stream);
+    }
+    SG_CHECK(copy_h2d(d + L.blk, h + L.blk, static_cast<size_t>(nb) * B, st.stream));
+    if (rx) SG_CHECK(copy_h2d(d + L.rows, h + L.rows, nb, st.stream));
+    if (mixed) SG_CHECK(copy_h2d(d + L.first, h + L.first, (gn + 1) * sizeof(int), st.stream));
+    return 0;
+}
+
+// Pinned and device bytes a bucket's slots need. The delivery-1 regions of every chunk start at
+// h_d1 / d_d1, behind the largest chunk's layout; the slot ends behind the largest such region.
+struct SlotBytes {
+    size_t h_d1 = 0, d_d1 = 0, nh = 0, nd = 0;
+};
+template <class LayoutOf>
+SlotBytes slot_bytes(const Chunks &ch, LayoutOf layout) {
+    SlotBytes b;
+    for (int c = 0; c < ch.chunks(); ++c) {
+        const SlotLayout L = layout(c);
+        b.h_d1 = std::max(b.h_d1, L.h_end);
+        b.d_d1 = std::max(b.d_d1, L.d_end);
+        b.nh = std::max(b.nh, L.h_d1n);
+        b.nd = std::max(b.nd, L.d_d1n);
+    }
+    b.nh += b.h_d1;
+    b.nd += b.d_d1;
+    return b;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Sender
@@ -367,128 +585,71 @@ bool tx_info(const ShorthairTxGroup &g, TxInfo &t) {
     return true;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Device framing (shorthair_groups_set_framing(1)). A chunk's pinned slot carries only what the GPU
-// cannot know, back to back, and goes over in one H2D copy:
-//   off[nb] (8 B each) | len[nb] (4 B) | first[gn + 1] (4 B, mixed-k buckets) | rows[nb] | raw[nb]
-//   (receiver) | pad to 16 | the payload bytes packed (recovery bodies among them, raw = 1)
-// shorthair_frame_batch builds blocks[nb][B] from it in a device-only region behind the copy, the
-// codec call of the host-framing route runs on those blocks, and the outputs follow them. The
-// pinned side holds the outputs right behind the copy (DevLayout::h2d rounded up to 16).
-// Buckets, chunk cuts (device bytes of blocks + outputs), launches and finishers are those of the
-// host-framing route.
-// ---------------------------------------------------------------------------------------------
-struct DevLayout {
-    size_t o_len, o_first, o_rows, o_raw, o_pay, h2d;  // h2d = o_pay + payload bytes
-};
-inline size_t up16(size_t x) { return (x + 15) & ~size_t(15); }
-DevLayout dev_layout(size_t nb, size_t gn, size_t pay, bool mixed, bool rx) {
-    DevLayout L;
-    L.o_len = 8 * nb;
-    L.o_first = L.o_len + 4 * nb;
-    L.o_rows = L.o_first + (mixed ? 4 * (gn + 1) : 0);
-    L.o_raw = L.o_rows + (rx ? nb : 0);
-    L.o_pay = up16(L.o_raw + (rx ? nb : 0));
-    L.h2d = L.o_pay + pay;
-    return L;
+// GenerateRecoveryBlock :598-608: "[k+i][k-1][m-1][block i]" for a group's m recovery blocks rec[m][B]
+void write_recovery_packets(ShorthairTxGroup &g, int m, int B, const uint8_t *rec) {
+    for (int y = 0; y < m; ++y) {
+        uint8_t *p = g.out + static_cast<size_t>(y) * g.out_stride;
+        p[0] = static_cast<uint8_t>(g.k + y);
+        p[1] = static_cast<uint8_t>(g.k - 1);
+        p[2] = static_cast<uint8_t>(m - 1);
+        std::memcpy(p + 3, rec + static_cast<size_t>(y) * B, B);
+    }
 }
 
-// Chunk c of a bucket is groups [start[c], start[c + 1]) of `ids`; blk0[j] / pay0[j] are the first
-// block and the first payload byte of group j counted from the bucket's start.
-struct DevChunks {
-    std::vector<int> start;
-    std::vector<long long> blk0, pay0;
-    int chunks() const { return static_cast<int>(start.size()) - 1; }
-    int g0(int c) const { return start[c]; }
-    int gn(int c) const { return start[c + 1] - start[c]; }
-    int nb(int c) const { return static_cast<int>(blk0[start[c + 1]] - blk0[start[c]]); }
-    size_t pay(int c) const { return static_cast<size_t>(pay0[start[c + 1]] - pay0[start[c]]); }
-};
-std::vector<int> uniform_chunks(int n, int per) {
-    std::vector<int> start;
-    for (int g = 0; g < n; g += per) start.push_back(g);
-    start.push_back(n);
-    return start;
-}
-
-int encode_bucket_dev(Staging &st, ShorthairTxGroup *groups, const std::vector<TxInfo> &info,
-                      const std::vector<int> &ids, int m, int B, int k, int kmax, bool mixed) {
-    const int n = static_cast<int>(ids.size());
+// One (K, m, B) bucket of the sender, groups `ids`, through the pipeline on framing route `framing`.
+int encode_bucket(Staging &st, int framing, ShorthairTxGroup *groups, const std::vector<TxInfo> &info,
+                  const std::vector<int> &ids, int m, int B) {
+    const BucketK bk = bucket_ks(info, ids);
     const size_t out_g = static_cast<size_t>(m) * B;
-    DevChunks ch;
-    if (mixed)
-        ch.start = var_chunks(ids, [&](int id) { return info[id].k; }, B, out_g + 4);
-    else
-        ch.start = uniform_chunks(n, static_cast<int>(std::max<size_t>(1, chunk_bytes() / (static_cast<size_t>(k) * B + out_g))));
-    ch.blk0.assign(n + 1, 0);
-    ch.pay0.assign(n + 1, 0);
-    for (int j = 0; j < n; ++j) {
-        const ShorthairTxGroup &g = groups[ids[j]];
-        long long p = 0;
-        for (int x = 0; x < g.k; ++x) p += g.lens[x];
-        ch.blk0[j + 1] = ch.blk0[j] + g.k;
-        ch.pay0[j + 1] = ch.pay0[j] + p;
-    }
-    size_t nh = 0, nd = 0;
-    for (int c = 0; c < ch.chunks(); ++c) {
-        const size_t head = up16(dev_layout(ch.nb(c), ch.gn(c), ch.pay(c), mixed, false).h2d);
-        nh = std::max(nh, head + ch.gn(c) * out_g);
-        nd = std::max(nd, head + static_cast<size_t>(ch.nb(c)) * B + ch.gn(c) * out_g);
-    }
+    std::function<long long(int)> pay_of;
+    if (framing == 1)
+        pay_of = [&](int id) {
+            long long p = 0;
+            for (int x = 0; x < groups[id].k; ++x) p += groups[id].lens[x];
+            return p;
+        };
+    const Chunks ch = plan_chunks(ids, bk.mixed, B, static_cast<size_t>(bk.k) * B + out_g, out_g + 4,
+                                  [&](int id) { return info[id].k; }, pay_of);
+    auto layout = [&](int c) {
+        return slot_layout(false, framing, bk.mixed, ch.nb(c), ch.gn(c), ch.pay(c), m, 0, B, false);
+    };
+    const SlotBytes sb = slot_bytes(ch, layout);
     auto prepare = [&](int c, Slot &s) {
-        const int g0 = ch.g0(c), gn = ch.gn(c);
-        const DevLayout L = dev_layout(ch.nb(c), gn, ch.pay(c), mixed, false);
+        const SlotLayout L = layout(c);
         uint8_t *h = static_cast<uint8_t *>(s.h);
-        long long *off = reinterpret_cast<long long *>(h);
-        int *len = reinterpret_cast<int *>(h + L.o_len), *first = reinterpret_cast<int *>(h + L.o_first);
-        if (mixed)
-            for (int j = 0; j <= gn; ++j) first[j] = static_cast<int>(ch.blk0[g0 + j] - ch.blk0[g0]);
-        parallel_for(gn, [&](int j) {
-            const ShorthairTxGroup &g = groups[ids[g0 + j]];
-            const long long b = ch.blk0[g0 + j] - ch.blk0[g0];
-            long long p = ch.pay0[g0 + j] - ch.pay0[g0];
-            for (int x = 0; x < g.k; ++x) {  // EncodeQueued :540-557: the payload only; the GPU frames it
-                const int l = g.lens[x];
-                off[b + x] = p;
-                len[b + x] = l;
-                framing_copy(h + L.o_pay + p, static_cast<const uint8_t *>(g.packets[x]), l);
-                p += l;
+        if (bk.mixed) ch.put_first(c, reinterpret_cast<int *>(h + L.first));
+        parallel_for(ch.gn(c), [&](int j) {
+            const ShorthairTxGroup &g = groups[ids[ch.g0(c) + j]];
+            long long p = ch.payoff(c, j);
+            for (int x = 0; x < g.k; ++x) {
+                put_block(framing, h, L, B, ch.blk(c, j) + x, p, g.packets[x], g.lens[x], false);
+                p += g.lens[x];
             }
             framing_fence();
         });
     };
-    auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
+    auto submit = [&](int c, Slot &s, std::function<int()> &fin) -> int {
         const int g0 = ch.g0(c), gn = ch.gn(c), nb = ch.nb(c);
-        const DevLayout L = dev_layout(nb, gn, ch.pay(c), mixed, false);
+        const SlotLayout L = layout(c);
         uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-        const size_t o_blk = up16(L.h2d), o_out = o_blk + static_cast<size_t>(nb) * B, h_out = up16(L.h2d);
-        SG_CHECK(copy_h2d(d, h, L.h2d, st.stream));
-        int rc = shorthair_frame_batch(B, nb, d + L.o_pay, static_cast<long long>(ch.pay(c)),
-                                       reinterpret_cast<const long long *>(d), reinterpret_cast<const int *>(d + L.o_len),
-                                       nullptr, d + o_blk, st.stream);
+        int rc = submit_inputs(st, s, framing, L, false, bk.mixed, nb, gn, ch.pay(c), B);
         if (rc != 0) return rc;
-        rc = mixed ? cauchy_256_encode_batch_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + L.o_first), nb,
-                                                 d + o_blk, d + o_out, st.stream)
-                   : cauchy_256_encode_batch(k, m, B, gn, d + o_blk, d + o_out, st.stream);
+        rc = bk.mixed ? cauchy_256_encode_batch_var(bk.kmax, m, B, gn, reinterpret_cast<const int *>(d + L.first), nb,
+                                                    d + L.blk, d + L.out, st.stream)
+                      : cauchy_256_encode_batch(bk.k, m, B, gn, d + L.blk, d + L.out, st.stream);
         if (rc != 0) return rc;
         count_launch(gn);
-        SG_CHECK(copy_d2h(h + h_out, d + o_out, gn * out_g, st.stream));
-        fin = [&, g0, gn, h, h_out, out_g]() {
-            parallel_for(gn, [&](int j) {  // GenerateRecoveryBlock :598-608: "[k+i][k-1][m-1][block i]"
-                ShorthairTxGroup &g = groups[ids[g0 + j]];
-                const uint8_t *rec = h + h_out + static_cast<size_t>(j) * out_g;
-                for (int y = 0; y < m; ++y) {
-                    uint8_t *p = g.out + static_cast<size_t>(y) * g.out_stride;
-                    p[0] = static_cast<uint8_t>(g.k + y);
-                    p[1] = static_cast<uint8_t>(g.k - 1);
-                    p[2] = static_cast<uint8_t>(m - 1);
-                    std::memcpy(p + 3, rec + static_cast<size_t>(y) * B, B);
-                }
+        SG_CHECK(copy_d2h(h + L.h_out, d + L.out, gn * out_g, st.stream));
+        const uint8_t *rec = h + L.h_out;
+        fin = [&, g0, gn, rec]() {
+            parallel_for(gn, [&](int j) {
+                write_recovery_packets(groups[ids[g0 + j]], m, B, rec + static_cast<size_t>(j) * out_g);
             });
+            return 0;
         };
         return 0;
     };
-    return pipeline(st, ch.chunks(), nh, nd, prepare, submit);
+    return pipeline(st, ch.chunks(), sb.nh, sb.nd, prepare, submit);
 }
 
 }  // namespace
@@ -533,126 +694,9 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
     Staging &st = staging();
     std::lock_guard<std::mutex> lock(st.mu);
     if (int rc = ensure_staging(st)) return rc;
-    for (auto &kv : buckets) {
-        const int m = std::get<1>(kv.first), B = std::get<2>(kv.first);
-        const std::vector<int> &ids = kv.second;
-        int k = info[ids[0]].k, kmax = k;
-        bool mixed = false;
-        for (int id : ids) {
-            mixed |= info[id].k != k;
-            kmax = std::max(kmax, info[id].k);
-        }
-        if (framing == 1) {
-            if (int rc = encode_bucket_dev(st, groups, info, ids, m, B, k, kmax, mixed)) return rc;
-            continue;
-        }
-        if (mixed) {
-            // One var-k launch per chunk. Slot: blocks packed | recovery [gn][m][B] | first[gn + 1]
-            const size_t out_g = static_cast<size_t>(m) * B;
-            const std::vector<int> start = var_chunks(ids, [&](int id) { return info[id].k; }, B, out_g + 4);
-            const int chunks = static_cast<int>(start.size()) - 1;
-            size_t max_blocks = 0, max_gn = 0;
-            std::vector<std::vector<int>> first(chunks);
-            for (int c = 0; c < chunks; ++c) {
-                first[c].push_back(0);
-                for (int j = start[c]; j < start[c + 1]; ++j) first[c].push_back(first[c].back() + info[ids[j]].k);
-                max_blocks = std::max<size_t>(max_blocks, first[c].back());
-                max_gn = std::max<size_t>(max_gn, start[c + 1] - start[c]);
-            }
-            const size_t o_out = (max_blocks * B + 15) & ~size_t(15), o_first = o_out + max_gn * out_g;
-            const size_t slot_bytes = o_first + (max_gn + 1) * sizeof(int);
-            auto prepare = [&](int c, Slot &s) {
-                const int g0 = start[c], gn = start[c + 1] - g0;
-                uint8_t *h = static_cast<uint8_t *>(s.h);
-                std::memcpy(h + o_first, first[c].data(), (gn + 1) * sizeof(int));
-                parallel_for(gn, [&](int j) {
-                    const ShorthairTxGroup &g = groups[ids[g0 + j]];
-                    uint8_t *blk = h + static_cast<size_t>(first[c][j]) * B;
-                    for (int x = 0; x < g.k; ++x, blk += B) {  // EncodeQueued :540-557, as below
-                        const int len = g.lens[x];
-                        put_u16(blk, len);
-                        framing_copy(blk + 2, static_cast<const uint8_t *>(g.packets[x]), len);
-                        std::memset(blk + 2 + len, 0, B - 2 - len);
-                    }
-                    framing_fence();
-                });
-            };
-            auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
-                const int g0 = start[c], gn = start[c + 1] - g0, total = first[c].back();
-                uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-                SG_CHECK(copy_h2d(d, h, static_cast<size_t>(total) * B, st.stream));
-                SG_CHECK(copy_h2d(d + o_first, h + o_first, (gn + 1) * sizeof(int), st.stream));
-                const int rc = cauchy_256_encode_batch_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + o_first),
-                                                           total, d, d + o_out, st.stream);
-                if (rc != 0) return rc;
-                count_launch(gn);
-                SG_CHECK(copy_d2h(h + o_out, d + o_out, gn * out_g, st.stream));
-                fin = [&, g0, gn, h]() {
-                    parallel_for(gn, [&](int j) {  // GenerateRecoveryBlock :598-608, as below
-                        ShorthairTxGroup &g = groups[ids[g0 + j]];
-                        const uint8_t *rec = h + o_out + static_cast<size_t>(j) * out_g;
-                        for (int y = 0; y < m; ++y) {
-                            uint8_t *p = g.out + static_cast<size_t>(y) * g.out_stride;
-                            p[0] = static_cast<uint8_t>(g.k + y);
-                            p[1] = static_cast<uint8_t>(g.k - 1);
-                            p[2] = static_cast<uint8_t>(m - 1);
-                            std::memcpy(p + 3, rec + static_cast<size_t>(y) * B, B);
-                        }
-                    });
-                };
-                return 0;
-            };
-            if (int rc = pipeline(st, chunks, slot_bytes, slot_bytes, prepare, submit)) return rc;
-            continue;
-        }
-        const size_t in_g = static_cast<size_t>(k) * B, out_g = static_cast<size_t>(m) * B;
-        const int per = static_cast<int>(std::max<size_t>(1, chunk_bytes() / (in_g + out_g)));
-        const int n = static_cast<int>(ids.size());
-        const int chunks = (n + per - 1) / per;
-        const size_t slot_bytes = static_cast<size_t>(std::min(per, n)) * (in_g + out_g);
-        auto prepare = [&](int c, Slot &s) {
-            const int g0 = c * per, gn = std::min(per, n - g0);
-            uint8_t *h = static_cast<uint8_t *>(s.h);
-            // EncodeQueued :540-557: "[len u16 LE][payload][zeros up to B]" per original
-            parallel_for(gn, [&](int j) {
-                const ShorthairTxGroup &g = groups[ids[g0 + j]];
-                uint8_t *blk = h + static_cast<size_t>(j) * in_g;
-                for (int x = 0; x < k; ++x, blk += B) {
-                    const int len = g.lens[x];
-                    put_u16(blk, len);
-                    framing_copy(blk + 2, static_cast<const uint8_t *>(g.packets[x]), len);
-                    std::memset(blk + 2 + len, 0, B - 2 - len);
-                }
-                framing_fence();
-            });
-        };
-        auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
-            const int g0 = c * per, gn = std::min(per, n - g0);
-            uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-            const size_t in_bytes = gn * in_g, out_bytes = gn * out_g;
-            SG_CHECK(copy_h2d(d, h, in_bytes, st.stream));
-            const int rc = cauchy_256_encode_batch(k, m, B, gn, d, d + in_bytes, st.stream);
-            if (rc != 0) return rc;
-            count_launch(gn);
-            SG_CHECK(copy_d2h(h + in_bytes, d + in_bytes, out_bytes, st.stream));
-            fin = [&, g0, gn, h, in_bytes]() {
-                // GenerateRecoveryBlock :598-608: "[k+i][k-1][m-1][block i]"
-                parallel_for(gn, [&](int j) {
-                    ShorthairTxGroup &g = groups[ids[g0 + j]];
-                    const uint8_t *rec = h + in_bytes + static_cast<size_t>(j) * out_g;
-                    for (int y = 0; y < m; ++y) {
-                        uint8_t *p = g.out + static_cast<size_t>(y) * g.out_stride;
-                        p[0] = static_cast<uint8_t>(k + y);
-                        p[1] = static_cast<uint8_t>(k - 1);
-                        p[2] = static_cast<uint8_t>(m - 1);
-                        std::memcpy(p + 3, rec + static_cast<size_t>(y) * B, B);
-                    }
-                });
-            };
-            return 0;
-        };
-        if (int rc = pipeline(st, chunks, slot_bytes, slot_bytes, prepare, submit)) return rc;
-    }
+    for (auto &kv : buckets)
+        if (int rc = encode_bucket(st, framing, groups, info, kv.second, std::get<1>(kv.first), std::get<2>(kv.first)))
+            return rc;
     return 0;
 }
 
@@ -698,47 +742,13 @@ int rx_info(const ShorthairRxGroup &g, RxInfo &r) {
     return 1;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Device delivery (shorthair_groups_set_delivery(1)), every m >= 2 bucket on both framing routes. After
-// the decode call shorthair_unframe_batch packs the chunk's delivered payloads in a device-only region
-// behind the slot's delivery-0 layout, and the D2H copy has two phases, as the host cannot know the
-// payload total before the decode:
-//   device region: payload[slots * min(B - 2, 65535)] | off[slots + 1] | len[slots] | scratch
-//   pinned region: total (8 B) | len[slots] (4 B each) | rows[slots] | pad to 16 | the packed payloads
-//   1. on the staging stream: len[], the decode's out rows and off[slots] (the total);
-//   2. in the finisher, after the slot's event: `total` packed bytes on Staging::stream2 -- nothing
-//      else is pending on the device for that region, and the staging stream keeps running the next
-//      chunk. The wait for that copy and the on_packet calls from the pinned packed buffer, in
-//      delivery 0's order, are the slot's `late` step: the pipeline runs it once the host threads have
-//      framed the slot's next chunk (which touches neither region), before that chunk is submitted.
-// ---------------------------------------------------------------------------------------------
-struct D1Layout {
-    size_t cap;                        // bytes of the packed-payload buffers
-    size_t d_off, d_len, d_scr, d_end;  // device region (the payload at 0)
-    size_t h_len, h_rows, h_pay, h_end;  // pinned region (the total at 0)
-};
-D1Layout d1_layout(size_t gn, int emax, int B) {
-    const size_t slots = gn * emax;
-    D1Layout L;
-    L.cap = slots * static_cast<size_t>(std::min(B - 2, 65535));
-    L.d_off = up16(L.cap);
-    L.d_len = L.d_off + 8 * (slots + 1);
-    L.d_scr = up16(L.d_len + 4 * slots);
-    L.d_end = L.d_scr + static_cast<size_t>(shorthair_unframe_scratch_bytes(static_cast<int>(gn), emax));
-    L.h_len = 16;
-    L.h_rows = L.h_len + 4 * slots;
-    L.h_pay = up16(L.h_rows + slots);
-    L.h_end = L.h_pay + L.cap;
-    return L;
-}
-
 // The delivery-1 tail of a chunk of gn groups (chunk-local group j = ids[g0 + j]) whose decode call has
 // been enqueued: d_out [gn][emax][B], d_orow [gn][emax], d_cnt [gn] in device memory; the regions
-// start d_base / h_base bytes into the slot. A failure in the finisher lands in *err.
+// start d_base / h_base bytes into the slot. A failure in the finisher is what it returns.
 int deliver1_tail(Staging &st, Slot &s, size_t d_base, size_t h_base, int B, int gn, int emax,
                   const uint8_t *d_out, const uint8_t *d_orow, const int *d_cnt,
                   const ShorthairRxGroup *groups, const std::vector<RxInfo> &info, const std::vector<int> &ids,
-                  int g0, shorthair_on_packet_fn on_packet, void *cb_ctx, int *err, std::function<void()> &fin) {
+                  int g0, shorthair_on_packet_fn on_packet, void *cb_ctx, std::function<int()> &fin) {
     const D1Layout L = d1_layout(gn, emax, B);
     const size_t slots = static_cast<size_t>(gn) * emax;
     uint8_t *h = static_cast<uint8_t *>(s.h) + h_base, *d = static_cast<uint8_t *>(s.d) + d_base;
@@ -754,20 +764,11 @@ int deliver1_tail(Staging &st, Slot &s, size_t d_base, size_t h_base, int B, int
     fin = [=, &s, &info, &ids]() {
         long long total;
         std::memcpy(&total, h, 8);
-        if (total < 0 || static_cast<unsigned long long>(total) > L.cap) {
-            *err = -2;
-            return;
-        }
-        if (total > 0 && copy_d2h(h + L.h_pay, d, static_cast<size_t>(total), second) != hipSuccess) {
-            *err = -2;
-            return;
-        }
+        if (total < 0 || static_cast<unsigned long long>(total) > L.cap) return -2;
+        if (total > 0 && copy_d2h(h + L.h_pay, d, static_cast<size_t>(total), second) != hipSuccess) return -2;
         s.late = [=, &info, &ids]() {
-            if (hipStreamSynchronize(second) != hipSuccess) {
-                *err = -2;
-                return;
-            }
-            if (!on_packet) return;
+            if (hipStreamSynchronize(second) != hipSuccess) return -2;
+            if (!on_packet) return 0;
             const int *len = reinterpret_cast<const int *>(h + L.h_len);
             const uint8_t *pay = h + L.h_pay;
             for (int j = 0; j < gn; ++j) {  // RecoverGroup :741-756; the prefix rule was applied on the GPU
@@ -780,147 +781,127 @@ int deliver1_tail(Staging &st, Slot &s, size_t d_base, size_t h_base, int B, int
                     pay += l;
                 }
             }
+            return 0;
         };
+        return 0;
     };
     return 0;
 }
 
-// Device framing, receiver (layout above): originals as payload bytes, the recovery packets' bodies
-// as raw blocks.
-int recover_bucket_dev(Staging &st, const ShorthairRxGroup *groups, const std::vector<RxInfo> &info,
-                       const std::vector<int> &ids, int m, int B, int k, int kmax, bool mixed,
-                       shorthair_on_packet_fn on_packet, void *cb_ctx, bool d1, int *d1_err) {
-    const int n = static_cast<int>(ids.size());
-    const int emax = std::min(mixed ? kmax : k, m);
-    const size_t out_g = m >= 2 ? static_cast<size_t>(emax) * B : static_cast<size_t>(B);
-    DevChunks ch;
-    if (mixed) {
-        ch.start = var_chunks(ids, [&](int id) { return info[id].k; }, B, out_g + emax + 8 + 256);
-    } else {
-        const size_t per_g = static_cast<size_t>(k) * B + k + out_g + emax + 4;
-        ch.start = uniform_chunks(n, static_cast<int>(std::max<size_t>(1, chunk_bytes() / per_g)));
+// Group g's k blocks and rows[] into the pinned slot from block x / payload byte p of its chunk: the
+// originals in arrival order (RecoverGroup :710-725), then the `use` recovery packets' blocks (:727-735).
+void put_rx_group(int framing, uint8_t *h, const SlotLayout &L, int B, const ShorthairRxGroup &g, int use,
+                  long long x, long long p) {
+    uint8_t *rows = h + L.rows, *raw = h + L.raw;  // raw[]: route 1 only
+    for (int i = 0; i < g.n_orig; ++i, ++x) {
+        rows[x] = g.orig_ids[i];
+        if (framing == 1) raw[x] = 0;
+        put_block(framing, h, L, B, x, p, g.orig_data[i], g.orig_lens[i], false);
+        p += g.orig_lens[i];
     }
-    ch.blk0.assign(n + 1, 0);
-    ch.pay0.assign(n + 1, 0);
-    for (int j = 0; j < n; ++j) {
-        const ShorthairRxGroup &g = groups[ids[j]];
-        const RxInfo &r = info[ids[j]];
-        long long p = static_cast<long long>(r.use) * B;
-        for (int i = 0; i < g.n_orig; ++i) p += g.orig_lens[i];
-        ch.blk0[j + 1] = ch.blk0[j] + r.k;
-        ch.pay0[j + 1] = ch.pay0[j] + p;
+    for (int i = 0; i < use; ++i, ++x, p += B) {
+        rows[x] = g.rec_packets[i][0];
+        if (framing == 1) raw[x] = 1;
+        put_block(framing, h, L, B, x, p, g.rec_packets[i] + 3, B, true);
     }
-    size_t nh = 0, nd = 0;
-    for (int c = 0; c < ch.chunks(); ++c) {
-        const size_t head = up16(dev_layout(ch.nb(c), ch.gn(c), ch.pay(c), mixed, true).h2d);
-        const size_t outs = ch.gn(c) * out_g + static_cast<size_t>(ch.gn(c)) * emax;
-        nh = std::max(nh, head + outs);
-        nd = std::max(nd, head + static_cast<size_t>(ch.nb(c)) * B + outs + 4 + ch.gn(c) * sizeof(int));
+    framing_fence();
+}
+
+// The host delivery of a chunk whose outputs are in the pinned slot (RecoverGroup :741-756): the
+// recovered blocks out[gn][out_g] whose length prefix fits, ids from orow[gn][emax] (m >= 2) or the
+// one missing original (m == 1).
+void deliver_host(const ShorthairRxGroup *groups, const std::vector<RxInfo> &info, const int *ids, int gn, int m,
+                  int emax, int B, const uint8_t *out, size_t out_g, const uint8_t *orow,
+                  shorthair_on_packet_fn on_packet, void *cb_ctx) {
+    for (int j = 0; j < gn; ++j) {
+        const int gi = ids[j];
+        const ShorthairRxGroup &g = groups[gi];
+        const int kg = info[gi].k, e = kg - g.n_orig;
+        int missing = -1;
+        if (m < 2) {
+            bool seen[256] = {false};
+            for (int i = 0; i < g.n_orig; ++i) seen[g.orig_ids[i]] = true;
+            for (int x = 0; x < kg && missing < 0; ++x)
+                if (!seen[x]) missing = x;
+        }
+        for (int i = 0; i < e; ++i) {
+            const uint8_t *blk = out + static_cast<size_t>(j) * out_g + static_cast<size_t>(i) * B;
+            const int id = m >= 2 ? orow[static_cast<size_t>(j) * emax + i] : missing;
+            const int len = static_cast<int>(get_u16(blk));
+            if (len <= B - 2) on_packet(cb_ctx, gi, id, blk + 2, len);
+        }
     }
-    const size_t h_d1 = up16(nh), d_d1 = up16(nd);  // device delivery: its regions behind the layout above
-    if (d1 && m >= 2) {
-        size_t max_gn = 0;
-        for (int c = 0; c < ch.chunks(); ++c) max_gn = std::max<size_t>(max_gn, ch.gn(c));
-        nh = h_d1 + d1_layout(max_gn, emax, B).h_end;
-        nd = d_d1 + d1_layout(max_gn, emax, B).d_end;
-    }
+}
+
+// One (K, m, B) bucket of the receiver, groups `ids`, through the pipeline on framing route `framing`;
+// d1: device delivery (m >= 2).
+int recover_bucket(Staging &st, int framing, bool d1, const ShorthairRxGroup *groups,
+                   const std::vector<RxInfo> &info, const std::vector<int> &ids, int m, int B,
+                   shorthair_on_packet_fn on_packet, void *cb_ctx) {
+    const BucketK bk = bucket_ks(info, ids);
+    const int emax = std::min(bk.kmax, m);
+    const size_t out_g = static_cast<size_t>(m >= 2 ? emax : 1) * B;
+    // per group: blocks k*B, rows k; out; out rows emax; count 4
+    std::function<long long(int)> pay_of;
+    if (framing == 1)
+        pay_of = [&](int id) {
+            long long p = static_cast<long long>(info[id].use) * B;
+            for (int i = 0; i < groups[id].n_orig; ++i) p += groups[id].orig_lens[i];
+            return p;
+        };
+    const Chunks ch = plan_chunks(ids, bk.mixed, B, static_cast<size_t>(bk.k) * B + bk.k + out_g + emax + 4,
+                                  out_g + emax + 8 + 256, [&](int id) { return info[id].k; }, pay_of);
+    auto layout = [&](int c) {
+        return slot_layout(true, framing, bk.mixed, ch.nb(c), ch.gn(c), ch.pay(c), m, emax, B, d1);
+    };
+    const SlotBytes sb = slot_bytes(ch, layout);
     auto prepare = [&](int c, Slot &s) {
-        const int g0 = ch.g0(c), gn = ch.gn(c);
-        const DevLayout L = dev_layout(ch.nb(c), gn, ch.pay(c), mixed, true);
+        const SlotLayout L = layout(c);
         uint8_t *h = static_cast<uint8_t *>(s.h);
-        long long *off = reinterpret_cast<long long *>(h);
-        int *len = reinterpret_cast<int *>(h + L.o_len), *first = reinterpret_cast<int *>(h + L.o_first);
-        uint8_t *rows = h + L.o_rows, *raw = h + L.o_raw;
-        if (mixed)
-            for (int j = 0; j <= gn; ++j) first[j] = static_cast<int>(ch.blk0[g0 + j] - ch.blk0[g0]);
-        parallel_for(gn, [&](int j) {
-            const ShorthairRxGroup &g = groups[ids[g0 + j]];
-            const RxInfo &r = info[ids[g0 + j]];
-            long long x = ch.blk0[g0 + j] - ch.blk0[g0];
-            long long p = ch.pay0[g0 + j] - ch.pay0[g0];
-            for (int i = 0; i < g.n_orig; ++i, ++x) {  // RecoverGroup :710-725: the payload only
-                const int l = g.orig_lens[i];
-                off[x] = p;
-                len[x] = l;
-                raw[x] = 0;
-                rows[x] = g.orig_ids[i];
-                framing_copy(h + L.o_pay + p, static_cast<const uint8_t *>(g.orig_data[i]), l);
-                p += l;
-            }
-            for (int i = 0; i < r.use; ++i, ++x) {  // :727-735: the packet's block, verbatim
-                off[x] = p;
-                len[x] = B;
-                raw[x] = 1;
-                rows[x] = g.rec_packets[i][0];
-                framing_copy(h + L.o_pay + p, g.rec_packets[i] + 3, B);
-                p += B;
-            }
-            framing_fence();
+        if (bk.mixed) ch.put_first(c, reinterpret_cast<int *>(h + L.first));
+        parallel_for(ch.gn(c), [&](int j) {
+            const int gi = ids[ch.g0(c) + j];
+            put_rx_group(framing, h, L, B, groups[gi], info[gi].use, ch.blk(c, j), ch.payoff(c, j));
         });
     };
-    auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
+    auto submit = [&](int c, Slot &s, std::function<int()> &fin) -> int {
         const int g0 = ch.g0(c), gn = ch.gn(c), nb = ch.nb(c);
-        const DevLayout L = dev_layout(nb, gn, ch.pay(c), mixed, true);
+        const SlotLayout L = layout(c);
         uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-        const size_t o_blk = up16(L.h2d), o_out = o_blk + static_cast<size_t>(nb) * B;
-        const size_t o_orow = o_out + gn * out_g, o_cnt = (o_orow + static_cast<size_t>(gn) * emax + 3) & ~size_t(3);
-        const size_t h_out = up16(L.h2d), h_orow = h_out + gn * out_g;
-        SG_CHECK(copy_h2d(d, h, L.h2d, st.stream));
-        int rc = shorthair_frame_batch(B, nb, d + L.o_pay, static_cast<long long>(ch.pay(c)),
-                                       reinterpret_cast<const long long *>(d), reinterpret_cast<const int *>(d + L.o_len),
-                                       d + L.o_raw, d + o_blk, st.stream);
+        int rc = submit_inputs(st, s, framing, L, true, bk.mixed, nb, gn, ch.pay(c), B);
         if (rc != 0) return rc;
+        int *d_cnt = reinterpret_cast<int *>(d + L.cnt);
+        if (m < 2)  // (a uniform bucket) the one erasure lands in place in block k-1 of each group
+            rc = cauchy_256_decode_batch(bk.k, m, B, gn, d + L.blk, d + L.rows, st.stream);
+        else if (bk.mixed)
+            rc = cauchy_256_decode_batch_out_var(bk.kmax, m, B, gn, reinterpret_cast<const int *>(d + L.first), nb,
+                                                 d + L.blk, d + L.rows, d + L.out, d + L.orow, d_cnt, st.stream);
+        else
+            rc = cauchy_256_decode_batch_out(bk.k, m, B, gn, d + L.blk, d + L.rows, d + L.out, d + L.orow, d_cnt,
+                                             st.stream);
+        if (rc != 0) return rc;
+        count_launch(gn);
+        if (d1)
+            return deliver1_tail(st, s, sb.d_d1, sb.h_d1, B, gn, emax, d + L.out, d + L.orow, d_cnt, groups, info, ids,
+                                 g0, on_packet, cb_ctx, fin);
         if (m >= 2) {
-            rc = mixed ? cauchy_256_decode_batch_out_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + L.o_first), nb,
-                                                         d + o_blk, d + L.o_rows, d + o_out, d + o_orow,
-                                                         reinterpret_cast<int *>(d + o_cnt), st.stream)
-                       : cauchy_256_decode_batch_out(k, m, B, gn, d + o_blk, d + L.o_rows, d + o_out, d + o_orow,
-                                                     reinterpret_cast<int *>(d + o_cnt), st.stream);
-            if (rc != 0) return rc;
-            count_launch(gn);
-            if (d1)
-                return deliver1_tail(st, s, d_d1, h_d1, B, gn, emax, d + o_out, d + o_orow,
-                                     reinterpret_cast<const int *>(d + o_cnt), groups, info, ids, g0, on_packet,
-                                     cb_ctx, d1_err, fin);
-            SG_CHECK(copy_d2h(h + h_out, d + o_out, gn * out_g, st.stream));
-            SG_CHECK(copy_d2h(h + h_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
+            SG_CHECK(copy_d2h(h + L.h_out, d + L.out, gn * out_g, st.stream));
+            SG_CHECK(copy_d2h(h + L.h_orow, d + L.orow, gn * static_cast<size_t>(emax), st.stream));
         } else {
-            // m == 1 (a uniform bucket): the one erasure lands in place in block k-1 of each group
-            rc = cauchy_256_decode_batch(k, m, B, gn, d + o_blk, d + L.o_rows, st.stream);
-            if (rc != 0) return rc;
-            count_launch(gn);
-            SG_CHECK(hipMemcpy2DAsync(h + h_out, B, d + o_blk + static_cast<size_t>(k - 1) * B, static_cast<size_t>(k) * B,
-                                      B, gn, hipMemcpyDeviceToHost, st.stream));
-            g_d2h.fetch_add(static_cast<long long>(gn) * B, std::memory_order_relaxed);
+            SG_CHECK(copy_d2h_2d(h + L.h_out, B, d + L.blk + static_cast<size_t>(bk.k - 1) * B,
+                                 static_cast<size_t>(bk.k) * B, B, gn, st.stream));
         }
-        if (!on_packet) {
-            fin = [] {};
+        // (decode only, no on_packet: the empty finisher still makes the pipeline wait for the chunk
+        // before the slot is reused and before the call returns)
+        const uint8_t *out = h + L.h_out, *orow = h + L.h_orow;
+        fin = [&, g0, gn, out, orow]() {
+            if (on_packet)
+                deliver_host(groups, info, ids.data() + g0, gn, m, emax, B, out, out_g, orow, on_packet, cb_ctx);
             return 0;
-        }
-        fin = [&, g0, gn, h, h_out, h_orow, out_g, emax]() {
-            for (int j = 0; j < gn; ++j) {  // RecoverGroup :741-756: deliver blocks whose length prefix fits
-                const int gi = ids[g0 + j];
-                const ShorthairRxGroup &g = groups[gi];
-                const int kg = info[gi].k, e = kg - g.n_orig;
-                const uint8_t *out = h + h_out + static_cast<size_t>(j) * out_g;
-                int missing = -1;
-                if (m < 2) {
-                    bool seen[256] = {false};
-                    for (int i = 0; i < g.n_orig; ++i) seen[g.orig_ids[i]] = true;
-                    for (int x = 0; x < kg && missing < 0; ++x)
-                        if (!seen[x]) missing = x;
-                }
-                for (int i = 0; i < e; ++i) {
-                    const uint8_t *blk = out + static_cast<size_t>(i) * B;
-                    const int id = m >= 2 ? h[h_orow + static_cast<size_t>(j) * emax + i] : missing;
-                    const int len = static_cast<int>(get_u16(blk));
-                    if (len <= B - 2) on_packet(cb_ctx, gi, id, blk + 2, len);
-                }
-            }
         };
         return 0;
     };
-    return pipeline(st, ch.chunks(), nh, nd, prepare, submit);
+    return pipeline(st, ch.chunks(), sb.nh, sb.nd, prepare, submit);
 }
 
 }  // namespace
@@ -930,7 +911,6 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
     if (count < 0 || (count > 0 && !groups)) return -1;
     const int framing = g_framing.load(std::memory_order_relaxed);
     const int delivery = g_delivery.load(std::memory_order_relaxed);
-    int d1_err = 0;  // a failure in a delivery-1 finisher
     std::vector<RxInfo> info(count);
     std::vector<int> kind(count);
     for (int i = 0; i < count; ++i)
@@ -954,209 +934,10 @@ extern "C" int shorthair_recover_groups(const ShorthairRxGroup *groups, int coun
     if (int rc = ensure_staging(st)) return rc;
     for (auto &kv : buckets) {
         const int m = std::get<1>(kv.first), B = std::get<2>(kv.first);
-        const std::vector<int> &ids = kv.second;
-        int k = info[ids[0]].k, kmax = k;
-        bool mixed = false;
-        for (int id : ids) {
-            mixed |= info[id].k != k;
-            kmax = std::max(kmax, info[id].k);
-        }
-        if (framing == 1) {
-            if (int rc = recover_bucket_dev(st, groups, info, ids, m, B, k, kmax, mixed, on_packet, cb_ctx,
-                                            delivery == 1 && m >= 2, &d1_err))
-                return rc;
-            if (d1_err) return d1_err;
-            decoded += static_cast<int>(ids.size());
-            continue;
-        }
-        if (mixed) {  // m >= 2 (bucket key)
-            // One var-k launch per chunk. Slot: blocks packed | rows packed | out [gn][emax][B] |
-            // out rows [gn][emax] | count [gn] | first[gn + 1]
-            const int emax = std::min(kmax, m);
-            const size_t out_g = static_cast<size_t>(emax) * B;
-            const std::vector<int> start = var_chunks(ids, [&](int id) { return info[id].k; }, B,
-                                                      out_g + emax + 8 + 256);
-            const int chunks = static_cast<int>(start.size()) - 1;
-            size_t max_blocks = 0, max_gn = 0;
-            std::vector<std::vector<int>> first(chunks);
-            for (int c = 0; c < chunks; ++c) {
-                first[c].push_back(0);
-                for (int j = start[c]; j < start[c + 1]; ++j) first[c].push_back(first[c].back() + info[ids[j]].k);
-                max_blocks = std::max<size_t>(max_blocks, first[c].back());
-                max_gn = std::max<size_t>(max_gn, start[c + 1] - start[c]);
-            }
-            const size_t o_rows = max_blocks * B, o_out = (o_rows + max_blocks + 15) & ~size_t(15);
-            const size_t o_orow = o_out + max_gn * out_g, o_cnt = (o_orow + max_gn * emax + 3) & ~size_t(3);
-            const size_t o_first = o_cnt + max_gn * sizeof(int);
-            const size_t slot_bytes = o_first + (max_gn + 1) * sizeof(int);
-            const bool d1 = delivery == 1;
-            const size_t base_d1 = up16(slot_bytes);  // device delivery: its regions behind the layout above
-            const size_t slot_h = d1 ? base_d1 + d1_layout(max_gn, emax, B).h_end : slot_bytes;
-            const size_t slot_d = d1 ? base_d1 + d1_layout(max_gn, emax, B).d_end : slot_bytes;
-            auto prepare = [&](int c, Slot &s) {
-                const int g0 = start[c], gn = start[c + 1] - g0;
-                uint8_t *h = static_cast<uint8_t *>(s.h);
-                std::memcpy(h + o_first, first[c].data(), (gn + 1) * sizeof(int));
-                parallel_for(gn, [&](int j) {
-                    const ShorthairRxGroup &g = groups[ids[g0 + j]];
-                    const RxInfo &r = info[ids[g0 + j]];
-                    uint8_t *blk = h + static_cast<size_t>(first[c][j]) * B;
-                    uint8_t *rows = h + o_rows + first[c][j];
-                    int x = 0;
-                    for (int i = 0; i < g.n_orig; ++i, ++x, blk += B) {  // RecoverGroup :710-725, as below
-                        const int len = g.orig_lens[i];
-                        put_u16(blk, len);
-                        framing_copy(blk + 2, static_cast<const uint8_t *>(g.orig_data[i]), len);
-                        std::memset(blk + 2 + len, 0, B - 2 - len);
-                        rows[x] = g.orig_ids[i];
-                    }
-                    for (int i = 0; i < r.use; ++i, ++x, blk += B) {  // :727-735
-                        framing_copy(blk, g.rec_packets[i] + 3, B);
-                        rows[x] = g.rec_packets[i][0];
-                    }
-                    framing_fence();
-                });
-            };
-            auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
-                const int g0 = start[c], gn = start[c + 1] - g0, total = first[c].back();
-                uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-                SG_CHECK(copy_h2d(d, h, static_cast<size_t>(total) * B, st.stream));
-                SG_CHECK(copy_h2d(d + o_rows, h + o_rows, total, st.stream));
-                SG_CHECK(copy_h2d(d + o_first, h + o_first, (gn + 1) * sizeof(int), st.stream));
-                const int rc = cauchy_256_decode_batch_out_var(kmax, m, B, gn, reinterpret_cast<const int *>(d + o_first),
-                                                               total, d, d + o_rows, d + o_out, d + o_orow,
-                                                               reinterpret_cast<int *>(d + o_cnt), st.stream);
-                if (rc != 0) return rc;
-                count_launch(gn);
-                if (d1)
-                    return deliver1_tail(st, s, base_d1, base_d1, B, gn, emax, d + o_out, d + o_orow,
-                                         reinterpret_cast<const int *>(d + o_cnt), groups, info, ids, g0, on_packet,
-                                         cb_ctx, &d1_err, fin);
-                SG_CHECK(copy_d2h(h + o_out, d + o_out, gn * out_g, st.stream));
-                SG_CHECK(copy_d2h(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
-                if (!on_packet) {
-                    fin = [] {};
-                    return 0;
-                }
-                fin = [&, g0, gn, h]() {
-                    for (int j = 0; j < gn; ++j) {  // RecoverGroup :741-756, as below
-                        const int gi = ids[g0 + j];
-                        const int e = info[gi].k - groups[gi].n_orig;
-                        const uint8_t *out = h + o_out + static_cast<size_t>(j) * out_g;
-                        for (int i = 0; i < e; ++i) {
-                            const uint8_t *blk = out + static_cast<size_t>(i) * B;
-                            const int id = h[o_orow + static_cast<size_t>(j) * emax + i];
-                            const int len = static_cast<int>(get_u16(blk));
-                            if (len <= B - 2) on_packet(cb_ctx, gi, id, blk + 2, len);
-                        }
-                    }
-                };
-                return 0;
-            };
-            if (int rc = pipeline(st, chunks, slot_h, slot_d, prepare, submit)) return rc;
-            if (d1_err) return d1_err;
-            decoded += static_cast<int>(ids.size());
-            continue;
-        }
-        const int emax = std::min(k, m);
-        // per group: blocks k*B, rows k; out emax*B; out rows emax; count 4 (m >= 2 only)
-        const size_t in_g = static_cast<size_t>(k) * B;
-        const size_t out_g = m >= 2 ? static_cast<size_t>(emax) * B : static_cast<size_t>(B);
-        const size_t per_g = in_g + k + out_g + emax + 4;
-        const int per = static_cast<int>(std::max<size_t>(1, chunk_bytes() / per_g));
-        const int n = static_cast<int>(ids.size());
-        const int chunks = (n + per - 1) / per;
-        const int cap = std::min(per, n);
-        const size_t slot_bytes = static_cast<size_t>(cap) * per_g + 64;
-        // slot layout (chunk of gn groups, offsets for cap groups): blocks | rows | out | out rows | count
-        // (device delivery reads d_out in 8-byte words: aligned then, within the 64 bytes of slack)
-        const bool d1 = delivery == 1 && m >= 2;
-        const size_t o_rows = cap * in_g, o_out = d1 ? up16(o_rows + cap * static_cast<size_t>(k)) : o_rows + cap * static_cast<size_t>(k);
-        const size_t o_orow = o_out + cap * out_g, o_cnt = (o_orow + cap * static_cast<size_t>(emax) + 3) & ~size_t(3);
-        const size_t base_d1 = up16(slot_bytes);  // device delivery: its regions behind the layout above
-        const size_t slot_h = d1 ? base_d1 + d1_layout(cap, emax, B).h_end : slot_bytes;
-        const size_t slot_d = d1 ? base_d1 + d1_layout(cap, emax, B).d_end : slot_bytes;
-        auto prepare = [&](int c, Slot &s) {
-            const int g0 = c * per, gn = std::min(per, n - g0);
-            uint8_t *h = static_cast<uint8_t *>(s.h);
-            parallel_for(gn, [&](int j) {
-                const ShorthairRxGroup &g = groups[ids[g0 + j]];
-                const RxInfo &r = info[ids[g0 + j]];
-                uint8_t *blk = h + static_cast<size_t>(j) * in_g;
-                uint8_t *rows = h + o_rows + static_cast<size_t>(j) * k;
-                int x = 0;
-                // RecoverGroup :710-725: originals "[len][payload]" zero-padded to B
-                for (int i = 0; i < g.n_orig; ++i, ++x, blk += B) {
-                    const int len = g.orig_lens[i];
-                    put_u16(blk, len);
-                    framing_copy(blk + 2, static_cast<const uint8_t *>(g.orig_data[i]), len);
-                    std::memset(blk + 2 + len, 0, B - 2 - len);
-                    rows[x] = g.orig_ids[i];
-                }
-                for (int i = 0; i < r.use; ++i, ++x, blk += B) {  // :727-735
-                    framing_copy(blk, g.rec_packets[i] + 3, B);
-                    rows[x] = g.rec_packets[i][0];
-                }
-                framing_fence();
-            });
-        };
-        auto submit = [&](int c, Slot &s, std::function<void()> &fin) -> int {
-            const int g0 = c * per, gn = std::min(per, n - g0);
-            uint8_t *h = static_cast<uint8_t *>(s.h), *d = static_cast<uint8_t *>(s.d);
-            SG_CHECK(copy_h2d(d, h, gn * in_g, st.stream));
-            SG_CHECK(copy_h2d(d + o_rows, h + o_rows, gn * static_cast<size_t>(k), st.stream));
-            if (m >= 2) {
-                const int rc = cauchy_256_decode_batch_out(k, m, B, gn, d, d + o_rows, d + o_out, d + o_orow,
-                                                           reinterpret_cast<int *>(d + o_cnt), st.stream);
-                if (rc != 0) return rc;
-                count_launch(gn);
-                if (d1)
-                    return deliver1_tail(st, s, base_d1, base_d1, B, gn, emax, d + o_out, d + o_orow,
-                                         reinterpret_cast<const int *>(d + o_cnt), groups, info, ids, g0, on_packet,
-                                         cb_ctx, &d1_err, fin);
-                SG_CHECK(copy_d2h(h + o_out, d + o_out, gn * out_g, st.stream));
-                SG_CHECK(copy_d2h(h + o_orow, d + o_orow, gn * static_cast<size_t>(emax), st.stream));
-            } else {
-                // m == 1 (cauchy_decode_m1): the one erasure lands in place in block k-1, the
-                // single recovery block (n_orig = k-1 originals precede it)
-                const int rc = cauchy_256_decode_batch(k, m, B, gn, d, d + o_rows, st.stream);
-                if (rc != 0) return rc;
-                count_launch(gn);
-                SG_CHECK(hipMemcpy2DAsync(h + o_out, B, d + static_cast<size_t>(k - 1) * B, in_g, B, gn,
-                                          hipMemcpyDeviceToHost, st.stream));
-                g_d2h.fetch_add(static_cast<long long>(gn) * B, std::memory_order_relaxed);
-            }
-            if (!on_packet) {  // decode only (no delivery): still wait for the chunk before the
-                fin = [] {};   // slot is reused and before the call returns
-                return 0;
-            }
-            fin = [&, g0, gn, h]() {
-                // RecoverGroup :741-756: deliver recovered blocks whose length prefix fits
-                for (int j = 0; j < gn; ++j) {
-                    const int gi = ids[g0 + j];
-                    const ShorthairRxGroup &g = groups[gi];
-                    const int e = k - g.n_orig;
-                    const uint8_t *out = h + o_out + static_cast<size_t>(j) * out_g;
-                    int missing = -1;
-                    if (m < 2) {
-                        bool seen[256] = {false};
-                        for (int i = 0; i < g.n_orig; ++i) seen[g.orig_ids[i]] = true;
-                        for (int x = 0; x < k && missing < 0; ++x)
-                            if (!seen[x]) missing = x;
-                    }
-                    for (int i = 0; i < e; ++i) {
-                        const uint8_t *blk = out + static_cast<size_t>(i) * B;
-                        const int id = m >= 2 ? h[o_orow + static_cast<size_t>(j) * emax + i] : missing;
-                        const int len = static_cast<int>(get_u16(blk));
-                        if (len <= B - 2) on_packet(cb_ctx, gi, id, blk + 2, len);
-                    }
-                }
-            };
-            return 0;
-        };
-        if (int rc = pipeline(st, chunks, slot_h, slot_d, prepare, submit)) return rc;
-        if (d1_err) return d1_err;
-        decoded += n;
+        if (int rc = recover_bucket(st, framing, delivery == 1 && m >= 2, groups, info, kv.second, m, B, on_packet,
+                                    cb_ctx))
+            return rc;
+        decoded += static_cast<int>(kv.second.size());
     }
     return decoded;
 }

@@ -288,3 +288,50 @@ def test_device_delivery_over_several_chunks():
     finally:
         sg.set_delivery(0)
         sg.set_framing(0)
+
+
+@pytest.mark.gpu
+def test_device_delivery_region_survives_a_larger_next_chunk():
+    """Four chunks of one bucket (k = 200, m = 32, B = 1400: 154 groups per chunk), so each slot is reused
+    while its previous chunk's `late` step is pending. The first two chunks carry short payloads and
+    lose one original per group; the last two carry full payloads, so their inputs are several times the
+    first two's inputs plus outputs. A chunk's pinned delivery-1 region (total, len[], rows, packed
+    payloads) is read after the slot's next chunk has been prepared, so it must lie behind the largest
+    chunk's layout, not the chunk's own: delivery 1 gives delivery 0's callbacks on both framing routes."""
+    import shorthair_amd as sh
+    from shorthair_amd import groups as sg
+    ora = po.oracle()
+    nprng = np.random.default_rng(23)
+    rng = random.Random(5)
+    per, k, m = 154, 200, 32
+    G = 3 * per + 60
+    groups, rx_e = [], []
+    for g in range(G):
+        short = g < 2 * per
+        lens = [int(v) for v in nprng.integers(0, 21, size=k)] if short else [1398] * k
+        lens[0] = 1398  # B = 1400
+        whole = nprng.integers(0, 256, size=sum(lens), dtype=np.uint8).tobytes()
+        cuts = np.concatenate([[0], np.cumsum(lens)])
+        groups.append((m, [whole[cuts[i]:cuts[i + 1]] for i in range(k)]))
+        rx_e.append(1 if short else rng.randint(1, m))
+    assert sg.set_framing(0) == 0 and sg.set_delivery(0) == 0
+    try:
+        recs = sg.encode_groups(groups)
+        rx = []
+        for (_, pk), rec, e in zip(groups, recs, rx_e):
+            lost = set(rng.sample(range(1, k), e))  # (the full-size original stays: small chunk inputs)
+            orig = [(i, pk[i]) for i in range(k) if i not in lost]
+            rng.shuffle(orig)
+            rx.append((orig, rng.sample(rec, e)))
+        host = _recover(sh, sg, rx)
+        assert host[0] == G and host[2] == (4, G)     # four chunks, a launch each
+        for framing in (0, 1):
+            sg.set_framing(framing)
+            sg.set_delivery(1)
+            dev = _recover(sh, sg, rx)
+            assert dev[:3] == host[:3], framing
+        for gi in (0, per, 2 * per, G - 1):
+            assert [(pid, p) for g, pid, p in host[1] if g == gi] == opk.rx_group(ora, *rx[gi])
+    finally:
+        sg.set_delivery(0)
+        sg.set_framing(0)

@@ -105,6 +105,17 @@ int shorthair_groups_set_framing(int where);
  * each shorthair_recover_groups call. */
 int shorthair_groups_set_delivery(int where);
 
+/* Where shorthair_encode_groups builds the recovery packets of its k >= 2 buckets. 0 = the bare recovery
+ * blocks cross PCIe and host threads write "[k+y][k-1][m-1]" in front of each while copying it into `out`
+ * (the default). 1 = the GPU does (shorthair_wire_emit_batch, shorthair_wire.h), after the codec call on
+ * the same stream, into a device-only region of the chunk's slot; the chunk's copy back brings exactly
+ * groups * m * (3 + block_bytes) bytes of records instead of the blocks, and the host copies a group's
+ * m records into `out` in one piece. Buckets, chunks, launches, wire bytes, m_out, out_stride and return
+ * codes are the same either way, on both framing routes; k == 1 groups stay on the host.
+ * Returns the previous value, -1 for any other argument (nothing changes). Read once at the start of
+ * each shorthair_encode_groups call. */
+int shorthair_groups_set_wire(int where);
+
 /* Cumulative bytes the two calls copied host->device and device->host since load. Either pointer may
  * be NULL. Returns 0. */
 int shorthair_groups_traffic(long long *h2d_bytes, long long *d2h_bytes);

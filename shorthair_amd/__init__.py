@@ -14,7 +14,7 @@ import os
 
 __all__ = ["lib", "Block", "CAUCHY_256_VERSION", "cauchy_256_init", "cauchy_256_encode",
            "cauchy_256_decode", "encode_batch", "decode_batch", "decode_batch_out",
-           "encode_batch_var", "decode_batch_out_var", "frame_batch", "unframe_batch", "unframe_scratch_bytes",
+           "encode_batch_var", "decode_batch_out_var", "frame_batch", "unframe_batch", "unframe_scratch_bytes", "wire_emit_batch",
            "UNFRAME_TILE_SLOTS", "UNFRAME_SCAN_PASS", "groups_stats",
            "fill_synthetic", "erasure_pattern", "batch_reserve", "batch_errors", "has_fixed", "path", "default_stream", "sync", "LIB_PATH",
            "EXPORTED_SYMBOLS"]
@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "shorthair_recovery_packet_bytes", "shorthair_encode_groups", "shorthair_recover_groups",
     "shorthair_groups_stats", "shorthair_groups_set_framing", "shorthair_groups_traffic",
     "shorthair_frame_batch", "shorthair_unframe_scratch_bytes", "shorthair_unframe_batch",
-    "shorthair_groups_set_delivery",
+    "shorthair_groups_set_delivery", "shorthair_wire_emit_batch", "shorthair_groups_set_wire",
 ]
 
 # include/shorthair_unframe.h: slots per tile sum, and tile sums the scan workgroup takes per pass
@@ -91,6 +91,8 @@ lib.shorthair_unframe_scratch_bytes.restype = _c.c_longlong
 lib.shorthair_unframe_batch.argtypes = ([_c.c_int] * 3 + [_c.c_longlong] + [_c.c_void_p] * 3 + [_c.c_longlong] +
                                         [_c.c_void_p] * 4)
 lib.shorthair_unframe_batch.restype = _c.c_int
+lib.shorthair_wire_emit_batch.argtypes = [_c.c_int] * 4 + [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 3
+lib.shorthair_wire_emit_batch.restype = _c.c_int
 lib.shorthair_groups_stats.argtypes = [_c.c_void_p, _c.c_void_p]
 lib.shorthair_groups_stats.restype = _c.c_int
 lib.cauchy_256_batch_reserve.argtypes = [_c.c_int] * 4
@@ -230,6 +232,18 @@ def unframe_batch(block_bytes, groups, emax, group_stride_blocks, out, out_count
     return _check(lib.shorthair_unframe_batch(block_bytes, groups, emax, group_stride_blocks, ptr(out),
                                               ptr(out_count), ptr(payload), payload_capacity, ptr(off),
                                               ptr(length), ptr(scratch), _stream(stream)), "unframe_batch")
+
+
+def wire_emit_batch(k, m, block_bytes, groups, first, total_blocks, recovery, wire, stream=None):
+    """Frame recovery blocks as wire packets on the GPU (include/shorthair_wire.h): record g * m + y of
+    wire [groups * m][3 + B] = [k_g + y][k_g - 1][m - 1][recovery[g][y]], k_g = k, or first[g + 1] -
+    first[g] with first int32 [groups + 1] (k is then kmax; a malformed group's records are zeros).
+    recovery uint8 [groups][m][B] (8-byte aligned), wire uint8 at any address: cuda tensors, or integer
+    device addresses; first a tensor, an address or None."""
+    def ptr(t):
+        return t if t is None or isinstance(t, int) else int(t.data_ptr())
+    return _check(lib.shorthair_wire_emit_batch(k, m, block_bytes, groups, ptr(first), total_blocks, ptr(recovery),
+                                                ptr(wire), _stream(stream)), "wire_emit_batch")
 
 
 def groups_stats():

@@ -24,12 +24,14 @@
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/shorthair_frame.h"
 #include "../../include/shorthair_unframe.h"
+#include "../../include/shorthair_wire.h"
 #include "cauchy_math.hpp"
 #include "colsnip.h"
 #include "frame.hpp"
 #include "kernels.hpp"
 #include "measure.hpp"
 #include "unframe.hpp"
+#include "wire.hpp"
 
 namespace {
 
@@ -1128,6 +1130,26 @@ extern "C" int shorthair_frame_batch(int block_bytes, int total_blocks, const vo
     std::lock_guard<std::mutex> g(st->mu);
     SH_CHECK(sh::launch_frame(block_bytes, total_blocks, static_cast<const uint8_t *>(d_payload), payload_bytes,
                               d_off, d_len, d_raw, static_cast<uint8_t *>(d_blocks), st->d_errors, s));
+    return 0;
+}
+
+extern "C" int shorthair_wire_emit_batch(int k, int m, int block_bytes, int groups, const int *d_first,
+                                         int total_blocks, const void *d_recovery, void *d_wire, void *stream) {
+    if (k < 2 || k > 255 || m < 1 || k + m > 256 || block_bytes < 8 || block_bytes % 8 != 0 || groups < 0) return -1;
+    if (static_cast<long long>(groups) * m > 0x7fffffffll) return -1;
+    if (d_first && (total_blocks < 0 || static_cast<long long>(total_blocks) > static_cast<long long>(groups) * k ||
+                    reinterpret_cast<uintptr_t>(d_first) % 4 != 0))
+        return -1;
+    if (groups > 0 && (!d_recovery || !d_wire)) return -1;
+    if (reinterpret_cast<uintptr_t>(d_recovery) % 8 != 0) return -1;
+    if (groups == 0) return 0;
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    // (no stream state: the call counts nothing and needs no workspace)
+    SH_CHECK(sh::launch_wire_emit(k, m, block_bytes, groups, d_first, total_blocks,
+                                  static_cast<const uint8_t *>(d_recovery), static_cast<uint8_t *>(d_wire),
+                                  pick(stream)));
     return 0;
 }
 

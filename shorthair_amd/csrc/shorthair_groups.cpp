@@ -21,6 +21,10 @@
 // shorthair_unframe_batch packs the recovered payloads of an m >= 2 chunk in device memory and only
 // they, their lengths and rows come back, in two copies; the callbacks are the same.
 //
+// shorthair_groups_set_wire(1) moves the sender's packet headers to the GPU: shorthair_wire_emit_batch
+// builds the "[k+y][k-1][m-1][block]" records of a chunk in device memory behind the codec's output, they
+// come back whole, and the finisher copies a group's m records in one piece.
+//
 // There is one copy of each thing for all routes: one chunk plan (Chunks), one slot layout per chunk
 // (slot_layout), one encode_bucket and one recover_bucket. The framing route decides only what
 // prepare writes into the pinned slot (put_block) and what is enqueued before the codec call
@@ -45,6 +49,7 @@
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/shorthair_frame.h"
 #include "../../include/shorthair_unframe.h"
+#include "../../include/shorthair_wire.h"
 #include "kernels.hpp"
 #include "measure.hpp"
 #include "../../include/shorthair_groups.h"
@@ -331,6 +336,10 @@ std::atomic<int> g_framing{0};
 // 1 = the GPU unframes them and only the packed payloads come back.
 std::atomic<int> g_delivery{0};
 
+// shorthair_groups_set_wire: 0 = bare recovery blocks come back and the host writes the packet headers,
+// 1 = the GPU emits the wire records and they come back whole.
+std::atomic<int> g_wire{0};
+
 // Bucket key of a group: the K of the compiled kernel that codes (k, m, B), or k itself.
 int bucket_k(int k, int m, int B) {
     const int K = sh::fixed_kernel_k(k, m, B);
@@ -465,17 +474,20 @@ D1Layout d1_layout(size_t gn, int emax, int B) {
 // follow the chunk's own end but the largest end among the bucket's chunks (slot_bytes), 16-byte
 // aligned: a chunk's pinned region is still read by its `late` step after the slot's next chunk has
 // been prepared, so no chunk's inputs or outputs may reach it.
+// Wire route 1 (sender): wire[gn * m][3 + B] follows the layout above on the device side, 16-byte aligned
+// and device only; on the pinned side the records take out's place, at h_out.
 // ---------------------------------------------------------------------------------------------
 struct SlotLayout {
     size_t off, len, first, rows, raw, pay, h2d;  // inputs (off, len, raw, pay, h2d: route 1 only)
     size_t blk, out, orow, cnt;                    // device side
+    size_t wire, wire_n;                           // device side, wire route 1: the records and their bytes
     size_t h_out, h_orow;                          // pinned side
     size_t out_g;                                  // out bytes per group
     size_t h_end, d_end;                           // 16-byte aligned ends of all of the above
     size_t h_d1n, d_d1n;                           // bytes of the chunk's delivery-1 regions (0 without)
 };
 SlotLayout slot_layout(bool rx, int framing, bool mixed, size_t nb, size_t gn, size_t pay, int m, int emax,
-                       int B, bool d1) {
+                       int B, bool d1, bool wire = false) {
     const size_t F = mixed ? 4 * (gn + 1) : 0, R = rx ? nb : 0, orows = rx ? gn * emax : 0;
     SlotLayout L{};
     L.out_g = static_cast<size_t>(rx ? (m >= 2 ? emax : 1) : m) * B;
@@ -499,6 +511,12 @@ SlotLayout slot_layout(bool rx, int framing, bool mixed, size_t nb, size_t gn, s
     L.cnt = (L.orow + orows + 3) & ~size_t(3);
     L.d_end = up16(L.cnt + (rx ? 4 * gn : 0));
     L.h_end = up16(L.h_orow + orows);
+    if (wire) {
+        L.wire = L.d_end;
+        L.wire_n = gn * m * (static_cast<size_t>(B) + 3);
+        L.d_end = up16(L.wire + L.wire_n);
+        L.h_end = up16(L.h_out + L.wire_n);
+    }
     L.d_d1n = d1 ? d1_layout(gn, emax, B).d_end : 0;
     L.h_d1n = d1 ? d1_layout(gn, emax, B).h_end : 0;
     return L;
@@ -596,8 +614,9 @@ void write_recovery_packets(ShorthairTxGroup &g, int m, int B, const uint8_t *re
     }
 }
 
-// One (K, m, B) bucket of the sender, groups `ids`, through the pipeline on framing route `framing`.
-int encode_bucket(Staging &st, int framing, ShorthairTxGroup *groups, const std::vector<TxInfo> &info,
+// One (K, m, B) bucket of the sender, groups `ids`, through the pipeline on framing route `framing`;
+// wire: the GPU emits the recovery packets.
+int encode_bucket(Staging &st, int framing, bool wire, ShorthairTxGroup *groups, const std::vector<TxInfo> &info,
                   const std::vector<int> &ids, int m, int B) {
     const BucketK bk = bucket_ks(info, ids);
     const size_t out_g = static_cast<size_t>(m) * B;
@@ -611,7 +630,7 @@ int encode_bucket(Staging &st, int framing, ShorthairTxGroup *groups, const std:
     const Chunks ch = plan_chunks(ids, bk.mixed, B, static_cast<size_t>(bk.k) * B + out_g, out_g + 4,
                                   [&](int id) { return info[id].k; }, pay_of);
     auto layout = [&](int c) {
-        return slot_layout(false, framing, bk.mixed, ch.nb(c), ch.gn(c), ch.pay(c), m, 0, B, false);
+        return slot_layout(false, framing, bk.mixed, ch.nb(c), ch.gn(c), ch.pay(c), m, 0, B, false, wire);
     };
     const SlotBytes sb = slot_bytes(ch, layout);
     auto prepare = [&](int c, Slot &s) {
@@ -639,11 +658,23 @@ int encode_bucket(Staging &st, int framing, ShorthairTxGroup *groups, const std:
                       : cauchy_256_encode_batch(bk.k, m, B, gn, d + L.blk, d + L.out, st.stream);
         if (rc != 0) return rc;
         count_launch(gn);
-        SG_CHECK(copy_d2h(h + L.h_out, d + L.out, gn * out_g, st.stream));
+        // wire route 1: the packets are built on the GPU and come back instead of the bare blocks
+        if (wire) {
+            rc = shorthair_wire_emit_batch(bk.mixed ? bk.kmax : bk.k, m, B, gn,
+                                           bk.mixed ? reinterpret_cast<const int *>(d + L.first) : nullptr, nb,
+                                           d + L.out, d + L.wire, st.stream);
+            if (rc != 0) return rc;
+        }
+        SG_CHECK(copy_d2h(h + L.h_out, d + (wire ? L.wire : L.out), wire ? L.wire_n : gn * out_g, st.stream));
         const uint8_t *rec = h + L.h_out;
-        fin = [&, g0, gn, rec]() {
+        const size_t wire_g = static_cast<size_t>(m) * (3 + B);  // a group's m records, laid out as g.out is
+        fin = [&, g0, gn, rec, wire_g]() {
             parallel_for(gn, [&](int j) {
-                write_recovery_packets(groups[ids[g0 + j]], m, B, rec + static_cast<size_t>(j) * out_g);
+                ShorthairTxGroup &g = groups[ids[g0 + j]];
+                if (wire)
+                    std::memcpy(g.out, rec + static_cast<size_t>(j) * wire_g, wire_g);
+                else
+                    write_recovery_packets(g, m, B, rec + static_cast<size_t>(j) * out_g);
             });
             return 0;
         };
@@ -664,6 +695,7 @@ extern "C" int shorthair_recovery_packet_bytes(int k, const unsigned short *lens
 extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
     if (count < 0 || (count > 0 && !groups)) return -1;
     const int framing = g_framing.load(std::memory_order_relaxed);
+    const bool wire = g_wire.load(std::memory_order_relaxed) == 1;
     std::vector<TxInfo> info(count);
     for (int i = 0; i < count; ++i) {
         if (!tx_info(groups[i], info[i])) return -1;
@@ -695,7 +727,8 @@ extern "C" int shorthair_encode_groups(ShorthairTxGroup *groups, int count) {
     std::lock_guard<std::mutex> lock(st.mu);
     if (int rc = ensure_staging(st)) return rc;
     for (auto &kv : buckets)
-        if (int rc = encode_bucket(st, framing, groups, info, kv.second, std::get<1>(kv.first), std::get<2>(kv.first)))
+        if (int rc = encode_bucket(st, framing, wire, groups, info, kv.second, std::get<1>(kv.first),
+                                   std::get<2>(kv.first)))
             return rc;
     return 0;
 }
@@ -956,6 +989,11 @@ extern "C" int shorthair_groups_set_framing(int where) {
 extern "C" int shorthair_groups_set_delivery(int where) {
     if (where != 0 && where != 1) return -1;
     return g_delivery.exchange(where, std::memory_order_relaxed);
+}
+
+extern "C" int shorthair_groups_set_wire(int where) {
+    if (where != 0 && where != 1) return -1;
+    return g_wire.exchange(where, std::memory_order_relaxed);
 }
 
 extern "C" int shorthair_groups_traffic(long long *h2d_bytes, long long *d2h_bytes) {

@@ -38,6 +38,8 @@ lib.shorthair_groups_set_framing.argtypes = [_c.c_int]
 lib.shorthair_groups_set_framing.restype = _c.c_int
 lib.shorthair_groups_set_delivery.argtypes = [_c.c_int]
 lib.shorthair_groups_set_delivery.restype = _c.c_int
+lib.shorthair_groups_set_wire.argtypes = [_c.c_int]
+lib.shorthair_groups_set_wire.restype = _c.c_int
 lib.shorthair_groups_traffic.argtypes = [_c.c_void_p, _c.c_void_p]
 lib.shorthair_groups_traffic.restype = _c.c_int
 
@@ -65,6 +67,16 @@ def set_delivery(where):
     prev = lib.shorthair_groups_set_delivery(where)
     if prev < 0:
         raise ValueError("set_delivery: 0 (host) or 1 (GPU)")
+    return prev
+
+
+def set_wire(where):
+    """Where encode_groups builds the recovery packets of its k >= 2 buckets: 0 = host threads write the
+    headers around the blocks that came back (default), 1 = the GPU emits the packets and they come back
+    whole. Returns the previous value; raises ValueError for anything else."""
+    prev = lib.shorthair_groups_set_wire(where)
+    if prev < 0:
+        raise ValueError("set_wire: 0 (host) or 1 (GPU)")
     return prev
 
 

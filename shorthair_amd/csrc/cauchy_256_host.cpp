@@ -96,10 +96,6 @@ struct StreamState {
     std::mutex mu;
     DevBuf ws;
     int *d_errors = nullptr;
-    // split-tile scratch of the compile-time kernels (lease_split), its own lock: a decode holds
-    // `mu` while it launches stage A, which takes this one too
-    std::mutex split_mu;
-    DevBuf split;
 };
 
 // One launch of the tile kernels: output rows [row0, row0 + nrows) with its snippet-address table.
@@ -263,41 +259,6 @@ int lease_workspace(Context &c, hipStream_t stream, size_t bytes, WsLease &out, 
     return 0;
 }
 
-// Split-tile scratch of a stream (fixed_common.hpp RowSink "Split tiles": the last tiles of a
-// compile-time launch run as two half-step workgroups whose partial rows meet here): 64 MB of
-// partials and one arrival counter per split tile, zeroed once when allocated (every launch
-// leaves them zero: the second arriver resets its tile's). Locked for one launch; launches on one
-// stream are ordered by the stream.
-constexpr size_t kSplitPartBytes = 64ull << 20;
-constexpr int kSplitMinGroups = 16;  // smaller batches: whole tiles (no scratch for the stream)
-// Only the A/B builds generate split-tile programs (tools/gen_fixed_kernels.py SH_SPLIT_GEN=1,
-// measured no faster: profiles/r06/ab_runs.txt block 2); the product never leases the scratch.
-#ifdef SH_MEASUREMENT_BUILD
-constexpr bool kSplitLaunch = true;
-#else
-constexpr bool kSplitLaunch = false;
-#endif
-constexpr int kSplitCounters = 4096;
-struct SplitLease {
-    std::unique_lock<std::mutex> lk;
-    uint8_t *part = nullptr;
-    uint32_t *cnt = nullptr;
-};
-int lease_split(Context &c, hipStream_t stream, SplitLease &out) {
-    StreamState *st = stream_state(c, stream);
-    if (!st) return -2;
-    out.lk = std::unique_lock<std::mutex>(st->split_mu);
-    if (!st->split.p) {
-        if (st->split.ensure(kSplitPartBytes + kSplitCounters * sizeof(uint32_t), stream)) return -2;
-        if (hipMemsetAsync(static_cast<uint8_t *>(st->split.p) + kSplitPartBytes, 0,
-                           kSplitCounters * sizeof(uint32_t), stream) != hipSuccess)
-            return -2;
-    }
-    out.part = static_cast<uint8_t *>(st->split.p);
-    out.cnt = reinterpret_cast<uint32_t *>(out.part + kSplitPartBytes);
-    return 0;
-}
-
 // Device generator for (k, m), m >= 2, k + m <= 256. Cached; created once per shape.
 uint8_t *generator(Context &c, int k, int m) {
     std::lock_guard<std::mutex> g(c.mu);
@@ -433,18 +394,10 @@ struct VarSpec {
 
 // One launch of a compile-time-scheduled kernel over the whole batch (the kernels build their
 // buffer descriptors per workgroup, so 32-bit offsets never limit the batch size).
-// split: the stream's split-tile scratch (nullptr: whole tiles only).
 hipError_t launch_fixed_batch(int k, int m, int B, int groups, const uint8_t *in, long long in_gs,
                               uint8_t *out, long long out_gs, const uint8_t *pos,
-                              const uint8_t *rpos, bool dec, hipStream_t s, const SplitLease *split = nullptr,
-                              const VarSpec *var = nullptr) {
+                              const uint8_t *rpos, bool dec, hipStream_t s, const VarSpec *var = nullptr) {
     sh::FixedArgs a{};
-    if (split) {
-        a.split_part = split->part;
-        a.split_cnt = split->cnt;
-        a.split_cap = static_cast<long long>(kSplitPartBytes);
-        a.split_max = kSplitCounters;
-    }
     a.in = in;
     a.in_gstride = in_gs;
     a.in_bytes = static_cast<long long>(groups) * in_gs;
@@ -556,12 +509,7 @@ int encode_batch(int k, int m, int B, int groups, const uint8_t *d_in, uint8_t *
     }
     const bool sliced = slice_scratch && groups == 1 && tile_usable(c, k, m, B) && latency_slices(k) > 1;
     if (sh::has_fixed(k, m, B) && !force_tile() && !sliced) {
-        SplitLease sp;
-        const bool split = kSplitLaunch && groups >= kSplitMinGroups;
-        if (split)
-            if (int rc = lease_split(c, s, sp)) return rc;
-        SH_CHECK(launch_fixed_batch(k, m, B, groups, d_in, in_gs, d_out, out_gs, nullptr, nullptr,
-                                    false, s, split ? &sp : nullptr));
+        SH_CHECK(launch_fixed_batch(k, m, B, groups, d_in, in_gs, d_out, out_gs, nullptr, nullptr, false, s));
         return 0;
     }
     if (tile_usable(c, k, m, B))
@@ -612,8 +560,7 @@ int encode_batch_var(int kmax, int m, int B, int groups, const VarSpec &var, con
         return 0;
     }
     if (sh::has_fixed(kmax, m, B) && !force_tile()) {
-        SH_CHECK(launch_fixed_batch(kmax, m, B, groups, d_in, 0, d_out, out_gs, nullptr, nullptr, false, s, nullptr,
-                                    &var));
+        SH_CHECK(launch_fixed_batch(kmax, m, B, groups, d_in, 0, d_out, out_gs, nullptr, nullptr, false, s, &var));
         return 0;
     }
     if (tile_usable(c, kmax, m, B))
@@ -863,13 +810,8 @@ int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_bl
         const bool sliced = slice_scratch && groups == 1 && tile_usable(c, k, m, B) && latency_slices(k + m) > 1 &&
                             w.kp == round4(k);
         if (sh::has_fixed(k, m, B) && !force_tile() && !sliced) {
-            SplitLease sp;
-            const bool split = kSplitLaunch && groups >= kSplitMinGroups && !var;
-            if (split)
-                if (int rc = lease_split(c, s, sp)) return rc;
             SH_CHECK(launch_fixed_batch(k, m, B, groups, d_blocks, static_cast<long long>(k) * B,
-                                        w.residual, static_cast<long long>(m) * B, w.pos, w.rpos, true, s,
-                                        split ? &sp : nullptr, var));
+                                        w.residual, static_cast<long long>(m) * B, w.pos, w.rpos, true, s, var));
         } else if (int rc = launch_tile_batch(c, k, m, B, groups, d_blocks, static_cast<long long>(k) * B,
                                               w.residual, static_cast<long long>(m) * B, w.pos, w.rpos, true, s,
                                               sliced ? slice_scratch : nullptr, var)) {

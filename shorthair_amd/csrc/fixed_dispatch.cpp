@@ -64,15 +64,6 @@ hipError_t module_launch(const char *tag, const FixedArgs &a, unsigned blocks, u
 #endif
 }
 
-bool tag_is_module(const char *tag) {
-#ifdef SH_MEASUREMENT_BUILD
-    static const char *dir = SH_MEASURE_ENV("SH_HSACO_DIR");
-    return dir && tag;
-#else
-    (void)tag;
-    return false;
-#endif
-}
 }  // namespace fixed
 
 // A kernel compiled for (K, m) also codes k < K: the generator's column x is the same for every k

@@ -110,9 +110,9 @@ def test_scheduled_xor_programs_compute_the_bitmatrix(k, m, joint, monkeypatch):
 
 @pytest.mark.parametrize("k,m", [(20, 16), (28, 4), (200, 32)])
 def test_split_tile_halves_sum_to_the_product(k, m):
-    """Split tiles (fixed_common.hpp RowSink "Split tiles"): the two half-step programs the
-    generator emits (steps cut at an even index, as gen_config does) compute partial products that
-    XOR to the whole bitmatrix product -- what the second arriving workgroup stores."""
+    """Body.emit on a partial step list: the programs emitted for two disjoint step ranges (the
+    steps cut at an even index, so the pair units are those of the whole program) compute partial
+    products that XOR to the whole bitmatrix product -- the product is linear in the steps."""
     g = _gen()
     rows = g.generator(k, m)
     steps = [("c", x) for x in range(k)]
@@ -128,3 +128,37 @@ def test_split_tile_halves_sum_to_the_product(k, m):
             want = sum(g.row_bytes(rows[y0 + yi][x])[b] << (8 * x) for x in range(k))
             assert parts[0][yi][b] ^ parts[1][yi][b] == want, (yi, b)
             assert parts[0][yi][b] >> (8 * n0) == 0  # half 0 touches blocks < n0 only
+
+
+def test_retired_kernel_forms_are_gone(tmp_path, monkeypatch):
+    """The A/B forms that lost their measurements (split tiles, persistent workgroups, StreamSrc,
+    the whole-block ring, part groups, the L2 prefetch, row pairs, residual init; DESIGN.md
+    §12/§13) are out of the product sources: no generator switch, no identifier, and the generated
+    units instantiate FIXED_KERNEL / FIXED_KERNEL_VAR with the shape arguments alone."""
+    import re
+    csrc = os.path.join(ROOT, "shorthair_amd", "csrc")
+    gen_py = os.path.join(ROOT, "tools", "gen_fixed_kernels.py")
+    sources = [gen_py] + [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))
+                          if f.endswith((".hpp", ".h", ".hip", ".cpp"))]
+    assert len(sources) > 10
+    for path in sources:
+        text = open(path).read()
+        for s in ("SH_PW", "SH_BLK", "SH_SPLIT", "SH_L2PF", "SH_ROW_PAIRS", "SH_PERSIST", "SH_STREAM", "SH_RINIT"):
+            assert s not in text, (s, path)
+    for f in ("fixed_common.hpp", "geometry.hpp", "cauchy_256_host.cpp"):
+        text = open(os.path.join(csrc, f)).read()
+        for s in ("BlkSrc", "BlkGeo", "StreamSrc", "SH_PERSISTENT_TILES", "split_part", "pf_stride"):
+            assert s not in text, (s, f)
+
+    g = _gen()
+    monkeypatch.setattr(g, "OUTDIR", str(tmp_path))
+    g.gen_config(28, 4)
+    assert "_half" not in (tmp_path / "fixed_k28_m4.inc").read_text()
+    want = {"enc": r"FIXED_KERNEL\(k28_m4, 28, 4, 1, 8, 4, 4, enc, false, true\)",
+            "dec": r"FIXED_KERNEL\(k28_m4, 28, 4, 1, 8, 4, 4, dec, true, true\)",
+            "encv": r"FIXED_KERNEL_VAR\(k28_m4, 28, 4, 1, 8, 4, 4, enc, false\)",
+            "decv": r"FIXED_KERNEL_VAR\(k28_m4, 28, 4, 1, 8, 4, 4, dec, true\)"}
+    for unit, pat in want.items():
+        lines = [ln for ln in (tmp_path / f"fixed_k28_m4_{unit}.hip").read_text().splitlines()
+                 if ln.startswith("FIXED_KERNEL")]
+        assert len(lines) == 1 and re.fullmatch(pat, lines[0]), (unit, lines)

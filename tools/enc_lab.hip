@@ -252,7 +252,7 @@ __device__ __forceinline__ void align_src(L &src) {
 template <int MODE, bool ST>
 __global__ __launch_bounds__(S::NT, 4) void kern(FixedArgs a, uint64_t *stamps, int ntiles) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    uint8_t *scratch = (MODE == 0 || MODE == 3) ? lds : lds + S::R * S::SLOT;
+    uint8_t *scratch = (MODE == 0 || MODE == 3) ? lds : lds + S::R * S::IMG;
     if (MODE != 2 && MODE != 6) {
         const int tile = xcd_tile(blockIdx.x, gridDim.x);
         LabSrc<false, ST> src;
@@ -376,7 +376,7 @@ int main(int argc, char **argv) {
     const int cus = prop.multiProcessorCount;
 
     struct V { const char *name; void (*k)(FixedArgs, uint64_t *, int); void (*ks)(FixedArgs, uint64_t *, int); size_t lds; int grid; };
-    const size_t ring = (size_t)S::R * S::SLOT, scr = (size_t)S::NW * 2048;
+    const size_t ring = (size_t)S::R * S::IMG, scr = (size_t)S::NW * 2048;
     std::vector<V> vs = {
         {"base", kern<0, false>, kern<0, true>, ring, ntiles},
 #ifdef LAB_MORE

@@ -170,7 +170,7 @@ class Body:
         self.lines = save
         return L
 
-    def emit(self, R, S, steps, KP, npf=0, st=0, group=None):
+    def emit(self, R, S, steps, KP, group=None):
         """group (SH_INTERLEAVE): the Body of every part; the wait / DMA / ring-read code is emitted
         once and each unit's XOR code as an if-chain over the parts, so the part-waves of a
         workgroup walk ONE region of code (each unit's parts adjacent) instead of P separate
@@ -185,10 +185,7 @@ class Body:
         next S steps and joins the workgroup barrier; every wave is then past the units before u,
         so the ring slots of their steps are free and are refilled (up to R steps ahead) right
         there. steps: ("c", x) = input column x (position-table entry x), ("r", y) = decode only:
-        the received recovery block of generator row y (entry KP + y), added to row y's residual.
-        npf > 0 (persistent encode): a tile after the first finds its steps 0..npf-1 already
-        issued by its predecessor, followed by that tile's epilogue stores (st per wave), so
-        waits for steps < npf count st more outstanding operations there."""
+        the received recovery block of generator row y (entry KP + y), added to row y's residual."""
         L = self.lines
         n = len(steps)
         dma = "nodma" not in ABLATE
@@ -217,48 +214,29 @@ class Body:
                     L.append(f"    src.read({t % R}, " + ", ".join(f"{bank}{8 * j + a}" for a in range(8)) + ");")
 
         nxt_issue = min(n, R - 1)  # steps 0..nxt_issue-1 issued (in order)
-        npf = min(npf, nxt_issue)
 
         def wait(T, I):
-            ex = st if T < npf else 0
-            return f"    src.template wait<{T}, {I}, {ex}>();" if ex else f"    src.template wait<{T}, {I}>();"
+            return f"    src.template wait<{T}, {I}>();"
 
         def consec(a, b):  # steps a..b-1 have consecutive position-table entries
             return all(tidx(steps[a + i]) == tidx(steps[a]) + i for i in range(b - a))
-        # Position entries are read 4 steps per LDS read, one burst of issues ahead (Src::pre4);
-        # the persistent form (npf > 0) keeps one read per step.
-        P4 = npf == 0
+        # Position entries are read 4 steps per LDS read, one burst of issues ahead (Src::pre4).
         if dma:
-            if npf:
-                L.append("    if (!src.pref) {")
-            for t in range(npf):
-                L.append(f"    src.issue({t}, src.pre({tidx(steps[t])}));")
-            if npf:
-                L.append("    } else {")
-                L.append("    src.images_done();")
-                L.append("    }")
-            if P4:
-                chunks = [(c, min(c + 4, nxt_issue)) for c in range(0, nxt_issue, 4)]
-                for c0, c1 in chunks:
-                    if consec(c0, c1):
-                        L.append(f"    const typename Src::Pre4 q{c0} = src.pre4({tidx(steps[c0])});")
-                for c0, c1 in chunks:
-                    for t in range(c0, c1):
-                        L.append(f"    src.issue4({t}, q{c0}, {t - c0});" if consec(c0, c1)
-                                 else f"    src.issue({t}, src.pre({tidx(steps[t])}));")
-            else:
-                for t in range(npf, nxt_issue):
-                    L.append(f"    src.issue({t}, src.pre({tidx(steps[t])}));")
+            chunks = [(c, min(c + 4, nxt_issue)) for c in range(0, nxt_issue, 4)]
+            for c0, c1 in chunks:
+                if consec(c0, c1):
+                    L.append(f"    const typename Src::Pre4 q{c0} = src.pre4({tidx(steps[c0])});")
+            for c0, c1 in chunks:
+                for t in range(c0, c1):
+                    L.append(f"    src.issue4({t}, q{c0}, {t - c0});" if consec(c0, c1)
+                             else f"    src.issue({t}, src.pre({tidx(steps[t])}));")
         need = units[1][-1] if len(units) > 1 else units[0][-1]
         landed = min(n - 1, max(need, S - 1), nxt_issue - 1)
         assert need <= landed
         L.append(wait(landed, nxt_issue))
         read_unit(0, "dA")
         if nxt_issue < n:
-            if P4:
-                L.append(f"    typename Src::Pre4 pre4 = src.pre4({tidx(steps[nxt_issue])});")
-            else:
-                L.append(f"    typename Src::Pre pre = src.pre({tidx(steps[nxt_issue])});")
+            L.append(f"    typename Src::Pre4 pre4 = src.pre4({tidx(steps[nxt_issue])});")
         b4 = nxt_issue  # first step covered by pre4
         for u, unit in enumerate(units):
             cur, nxt = ("dA", "dB") if u % 2 == 0 else ("dB", "dA")
@@ -279,19 +257,15 @@ class Body:
                         L.append(wait(landed, nxt_issue))
                     issued = False
                     while nxt_issue < n and nxt_issue - R <= unit[0] - 1:
-                        if dma and P4:
+                        if dma:
                             x = nxt_issue
                             if x - b4 < 4 and consec(b4, x + 1):
                                 L.append(f"    src.issue4({x}, pre4, {x - b4});")
                             else:
                                 L.append(f"    src.issue({x}, src.pre({tidx(steps[x])}));")
-                        elif dma:
-                            L.append(f"    src.issue({nxt_issue}, pre);")
                         nxt_issue += 1
                         issued = True
-                        if nxt_issue < n and not P4:
-                            L.append(f"    pre = src.pre({tidx(steps[nxt_issue])});")
-                    if P4 and issued and nxt_issue < n:
+                    if issued and nxt_issue < n:
                         L.append(f"    pre4 = src.pre4({tidx(steps[nxt_issue])});")
                         b4 = nxt_issue
                 if not READ_LATE:
@@ -526,78 +500,13 @@ def shape(k, m):
     # LDS per workgroup: ring of R slots (the 2 KB per wave of store scratch aliases the ring after
     # the last step)
     slot = 8 * CW * 64 * 4
-    if blk_sub(k, m):  # BlkSrc: NG whole block images per slot (fixed_common.hpp BlkGeo)
-        sub = blk_sub(k, m)
-        nq = (((sub + 3) // 4) + 3) & ~3
-        gs = ((8 * sub) + 15) & ~15
-        while (gs // 4) % 32 != nq % 32:
-            gs += 16
-        ng = (127 + nq - 1) // nq + 1
-        slot = -(-ng * gs // 1024) * 1024
     rmax = int(os.environ.get("SH_RING_MAX", "19" if rbytes <= 65536 else "16"))
     R = int(os.environ.get("SH_RING", str(max(3, min(rmax, rbytes // slot, max(76 * 1024, rbytes) // slot)))))
     rows = (m + P - 1) // P
     minw = int(os.environ.get("SH_MIN_WAVES", minw_default or ("2" if rows > 12 else ("3" if rows > 8 else "4"))))
     # blocks per barrier: R >= 2*SYNC + 1 keeps >= 1 group of DMA in flight past the one waited for
     sync = int(os.environ.get("SH_SYNC", str(max(1, min(4, (R - 1) // 2 - 1)))))
-    if stream_mode(P):
-        R = int(os.environ.get("SH_STREAM_R", "6"))  # register buffers: steps loaded ahead
     return P, CW, R, minw, sync
-
-
-def parts_per_wg(P):
-    """Parts per workgroup (fixed_common.hpp Shape::PW). A/B switch SH_PW: the P parts of a tile
-    run in P / SH_PW workgroups, each with its own ring over the whole tile (one or two code
-    streams per workgroup for P / PW times the input reads through L2). Default: all P."""
-    pw = int(os.environ.get("SH_PW", "0")) or P
-    return pw if P % pw == 0 else P
-
-
-def blk_sub(k, m):
-    """Whole-block input ring (fixed_common.hpp BlkSrc) for B = 8 * SH_BLK, A/B switch: the
-    kernel then serves that block size only. 0 = the sub-block-row gather (Src)."""
-    return int(os.environ.get("SH_BLK", "0"))
-
-
-def split_tiles(mode, k, P, pers):
-    """Split-tile programs (fixed_common.hpp RowSink "Split tiles": the launch's last tiles run
-    as two half-step workgroups combined in-launch), A/B switch SH_SPLIT_GEN=1: bit-exact but no
-    faster (profiles/r06/ab_runs.txt block 2), and the half programs triple the generated code
-    and the build time, so the product generates none."""
-    if os.environ.get("SH_SPLIT_GEN", "0") != "1" or pers or RINIT or INTERLEAVE or stream_mode(P):
-        return False
-    return k >= 16
-
-
-# A/B switch SH_ROW_PAIRS=1: two rows per epilogue barrier (RowSink::row2)
-ROW_PAIRS = os.environ.get("SH_ROW_PAIRS", "0") == "1"
-# A/B switch SH_L2PF=N: encode epilogues touch the first N steps of a later tile (Src::l2_prefetch)
-L2PF = int(os.environ.get("SH_L2PF", "0"))
-
-PERSIST = os.environ.get("SH_PERSIST", "0") == "1"
-# Decode stage A, SH_RINIT=1 (measured, not the default): residual rows start as the recovery
-# blocks R_y, loaded into the accumulators in the prologue (Src::rrow) instead of m extra ring
-# steps -- same time (ab_runs.txt block 7), but the per-lane dword loads fetch those rows at
-# ~1.6x their bytes (stage A reads 2.63 vs 2.42 GB per launch).
-RINIT = os.environ.get("SH_RINIT", "0") == "1"
-
-
-PERSIST_DEC = os.environ.get("SH_PERSIST_DEC", "1") == "1"
-
-
-def persistent(mode, P, R):
-    """Persistent workgroups with next-tile prefetch (fixed_common.hpp SH_PERSISTENT_TILES) for
-    kernels whose ring keeps >= 4 slots below the 2P row images; decode stage A stages the next
-    tile's position tables into LDS at the end of each tile."""
-    return (PERSIST and (mode == "enc" or PERSIST_DEC) and not stream_mode(P) and R - 2 * P >= 4
-            and "nodma" not in ABLATE)
-
-
-def stream_mode(P):
-    """One-part shapes may load each lane's words straight into registers (StreamSrc in
-    fixed_common.hpp) instead of through the LDS ring."""
-    mode = os.environ.get("SH_STREAM", "0")
-    return mode == "all" or (P == 1 and mode == "1")
 
 
 def gen_config(k, m):
@@ -621,96 +530,38 @@ def gen_config(k, m):
            "namespace fixed {",
            ""]
     KP = (k + 3) & ~3
-    pers = {mode: persistent(mode, P, R) for mode in ("enc", "dec")}
-    split = {mode: split_tiles(mode, k, P, pers[mode]) for mode in ("enc", "dec")}
     for mode in ("enc", "dec"):
-        rinit = mode == "dec" and RINIT and not pers[mode]
-        steps = [("c", x) for x in range(k)] + ([("r", y) for y in range(m)] if mode == "dec" and not rinit else [])
-        if INTERLEAVE and not pers[mode] and not rinit and len(parts) > 1:
+        steps = [("c", x) for x in range(k)] + ([("r", y) for y in range(m)] if mode == "dec" else [])
+        if INTERLEAVE and len(parts) > 1:
             out.extend(interleaved_function(name, mode, k, rows, parts, R, sync, steps, KP))
-            out.extend(["template <class Src, class Snk>",
-                        f"__device__ __forceinline__ void run_{name}_{mode}_half(int half, int part, const Src &src, const Snk &sink) {{",
-                        f"    run_{name}_{mode}(part, src, sink);", "}", ""])
             continue
         nrmax = max(b - a for a, b in parts)
-
-        def body_fn(fname, p, y0, y1, sub_steps, split_half=None, step0=0):
-            """One part's straight-line function over sub_steps; split_half: the epilogue stores a
-            partial and the second arriving half combines (RowSink "Split tiles")."""
-            # epilogue stores per wave: two 16-byte pieces per row of its part (RowSink::row)
-            npf = R - 2 * P if pers[mode] else 0
-            body = Body(k, rows, y0, y1, nrmax, part=p).emit(R, sync, sub_steps, KP, npf=npf,
-                                                             st=2 * (y1 - y0))
+        for p, (y0, y1) in enumerate(parts):  # one straight-line function per part
+            body = Body(k, rows, y0, y1, nrmax, part=p).emit(R, sync, steps, KP)
             nr = y1 - y0
             out.append(f"template <class Src, class Snk>")
-            out.append(f"__device__ __forceinline__ void {fname}(const Src &src, const Snk &sink) {{")
+            out.append(f"__device__ __forceinline__ void run_{name}_{mode}_p{p}(const Src &src, const Snk &sink) {{")
             out.append(f"    uint32_t acc[{nr}][8];")
-            if step0:
-                out.append(f"    src.set_step0({step0});  // encode: this half's first input block")
             # opaque zeros: a constant 0 would be folded into the first step, whose pinned results
             # then need register copies of shared table entries (AGPR spills at k=200).
-            if rinit:
-                out.extend(f"    src.rrow({y0 + yi}, acc[{yi}]);" for yi in range(nr))
-            else:
-                out.append(f"    for (int y = 0; y < {nr}; ++y) for (int b = 0; b < 8; ++b) ZERO(acc[y][b]);")
+            out.append(f"    for (int y = 0; y < {nr}; ++y) for (int b = 0; b < 8; ++b) ZERO(acc[y][b]);")
             out.append(body)
             out.append("    __builtin_amdgcn_sched_barrier(0);")
-            out.append(f"    // epilogue: store rows {y0}..{y1 - 1}" + (" (partial of a split tile)" if split_half is not None else ""))
+            out.append(f"    // epilogue: store rows {y0}..{y1 - 1}")
             out.append("    src.release();  // the store scratch aliases the ring")
-            if L2PF and mode == "enc" and not pers[mode] and split_half is None:
-                out.append(f"    const auto l2pf = src.template l2_prefetch<{L2PF}>();  // A/B: warm L2 for a later tile")
-            if pers[mode]:
-                out.append(f"    src.prefetch_next({R - 2 * P});  // the next tile's first steps")
             out.append("    sink.prepare();")
-            # row pairs (A/B switch): not with the persistent form (its images sit in the ring's
-            # top 2P slots) nor the split tiles' partial rows
-            pairs = ROW_PAIRS and not pers[mode] and split_half is None and 4 * parts_per_wg(P) <= R
             for yi in range(nrmax):  # every part joins the same number of row barriers
                 out.append("    __builtin_amdgcn_sched_barrier(0);")
-                last = "true" if yi == nrmax - 1 else "false"
-                if yi >= nr and pairs:
-                    out.append(f"    sink.template pad2<{yi}, {last}>();")
-                elif yi >= nr:
+                if yi >= nr:
                     out.append(f"    sink.template pad<{yi}>();")
                 elif "halfstore" in ABLATE and p >= len(parts) // 2:
                     out.append(f"    asm volatile(\"\" :: " + ", ".join(f'"v"(acc[{yi}][{b}])' for b in range(8)) + ");")
                 elif "nostore" in ABLATE:
                     out.append(f"    asm volatile(\"\" :: " + ", ".join(f'"v"(acc[{yi}][{b}])' for b in range(8)) + ");")
-                elif split_half is not None:
-                    out.append(f"    sink.template part_row<{yi}>({y0 + yi}, acc[{yi}]);")
-                elif pairs:
-                    out.append(f"    sink.template row2<{yi}, {last}>({y0 + yi}, acc[{yi}]);")
                 else:
                     out.append(f"    sink.template row<{yi}>({y0 + yi}, acc[{yi}]);")
-            if split_half is not None:
-                out.append(f"    sink.combine({y0}, {nr});")
-            if L2PF and mode == "enc" and not pers[mode] and split_half is None:
-                out.append("    src.l2_done(l2pf);  // the compiler's counted wait: the prefetch loads only")
             out.append("}")
             out.append("")
-
-        for p, (y0, y1) in enumerate(parts):
-            body_fn(f"run_{name}_{mode}_p{p}", p, y0, y1, steps)
-        # Split tiles: two half-step programs per part (the steps cut at an even index, so the
-        # pair units and their XOR programs are those of the whole program)
-        n0 = (len(steps) // 2) & ~1
-        if split[mode]:
-            for h, (sub, x0) in enumerate(((steps[:n0], 0), (steps[n0:], n0 if mode == "enc" else 0))):
-                for p, (y0, y1) in enumerate(parts):
-                    body_fn(f"run_{name}_{mode}_h{h}_p{p}", p, y0, y1, sub, split_half=h, step0=x0)
-        out.append(f"template <class Src, class Snk>")
-        out.append(f"__device__ __forceinline__ void run_{name}_{mode}_half(int half, int part, const Src &src, const Snk &sink) {{")
-        if split[mode]:
-            for h in (0, 1):
-                out.append(f"    {'if' if h == 0 else 'else if'} (half == {h}) {{")
-                for p in range(len(parts)):
-                    kw = "if" if p == 0 else "else if"
-                    out.append(f"        {kw} (part == {p}) run_{name}_{mode}_h{h}_p{p}(src, sink);")
-                out.append("    }")
-        else:  # never launched with split tiles (FIXED_KERNEL SPLIT = 0)
-            out.append(f"    run_{name}_{mode}(part, src, sink);")
-        out.append("}")
-        out.append("")
         out.append(f"template <class Src, class Snk>")
         out.append(f"__device__ __forceinline__ void run_{name}_{mode}(int part, const Src &src, const Snk &sink) {{")
         if "samecode" in ABLATE:  # timing only: every part-wave runs part 0's code (one code stream)
@@ -729,28 +580,25 @@ def gen_config(k, m):
     with open(inc, "w") as f:
         f.write("\n".join(out) + "\n")
     # One translation unit per kernel (encode / decode stage A): each is a ~30K-instruction
-    # straight-line function, so the build compiles them in parallel.
+    # straight-line function, so the build compiles them in parallel. The var-k form
+    # (FIXED_KERNEL_VAR: per-group source base and k, cauchy_256_*_var) gets a
+    # translation unit of its own, over the same generated program; the measurement-only nodma
+    # ablation has none: its launcher reports "not supported".
+    dma = "false" if "nodma" in ABLATE else "true"
+    args = f"{name}, {k}, {m}, {P}, {CW}, {R}, {minw}"
     paths = []
     for mode, dec in (("enc", "false"), ("dec", "true")):
         path = os.path.join(OUTDIR, f"fixed_{name}_{mode}.hip")
         with open(path, "w") as f:
             f.write(f"// GENERATED by tools/gen_fixed_kernels.py -- do not edit. (k={k}, m={m}, {mode})\n"
                     f'#include "fixed_{name}.inc"\n'
-                    + (f"FIXED_KERNEL_PERSISTENT({name}, {k}, {m}, {P}, {CW}, {R}, {minw}, {mode}, {dec})\n" if pers[mode] else
-                       f"FIXED_KERNEL({name}, {k}, {m}, {P}, {CW}, {R}, {minw}, {mode}, {dec}, "
-                       f"{'false' if 'nodma' in ABLATE else 'true'}, {'true' if stream_mode(P) else 'false'}, "
-                       f"{parts_per_wg(P)}, {blk_sub(k, m)}, {1 if split[mode] else 0})\n"))
+                    f"FIXED_KERNEL({args}, {mode}, {dec}, {dma})\n")
         paths.append(path)
-        # The var-k form (FIXED_KERNEL_VAR: per-group source base and k, cauchy_256_*_var) in a
-        # translation unit of its own, over the same generated program. The measurement-only
-        # sources and launch forms have none: their launcher reports "not supported".
-        var_ok = not (pers[mode] or stream_mode(P) or blk_sub(k, m) or "nodma" in ABLATE
-                      or parts_per_wg(P) != P)
         path = os.path.join(OUTDIR, f"fixed_{name}_{mode}v.hip")
         with open(path, "w") as f:
             f.write(f"// GENERATED by tools/gen_fixed_kernels.py -- do not edit. (k={k}, m={m}, {mode}, var-k)\n"
                     f'#include "fixed_{name}.inc"\n'
-                    + (f"FIXED_KERNEL_VAR({name}, {k}, {m}, {P}, {CW}, {R}, {minw}, {mode}, {dec})\n" if var_ok else
+                    + (f"FIXED_KERNEL_VAR({args}, {mode}, {dec})\n" if "nodma" not in ABLATE else
                        "namespace sh {\nnamespace fixed {\n"
                        f"hipError_t launch_{name}_{mode}v(FixedArgs, hipStream_t) {{ return hipErrorNotSupported; }}\n"
                        "}\n}\n"))

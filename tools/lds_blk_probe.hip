@@ -1,5 +1,5 @@
 // Measurement only (never part of the product): cost of the whole-block ring's LDS reads
-// (BlkSrc, fixed_common.hpp) -- ds_read_b32 at a * SUB + per-lane column bytes -- against the
+// (the retired BlkSrc source) -- ds_read_b32 at a * SUB + per-lane column bytes -- against the
 // sub-block-row layout's aligned reads. Modes (lane L of a wave, read a = 0..7):
 //   0 aligned, one run:            4L + 256a
 //   1 one run, misaligned uniform: 4L + 175a

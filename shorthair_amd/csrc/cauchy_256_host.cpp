@@ -589,10 +589,10 @@ int encode_batch_var(int kmax, int m, int B, int groups, const VarSpec &var, con
 
 // Workspace carve for decode of `groups` groups.
 struct DecodeWS {
-    bool fixed;       // stage A by a compile-time-scheduled kernel, stage B by stageb_fixed
-    bool small;       // ... and stage B by stageb_small (nq <= 16 word columns: byte coefficients)
-    bool v2;          // ... or by stageb_v2 (byte coefficients, one workgroup per group chunk)
-    int emax, ldA, ldB, nres;  // nres: residual rows per group (m when fixed, else emax)
+    bool full_residual;     // stage A (compile-time or tile kernels) leaves all m residual rows, and
+                            // the setup writes position tables instead of stage-A coefficients
+    sh::StageBRoute route;  // stage-B kernel (stageb_route.hpp); Snip iff !full_residual
+    int emax, ldA, ldB, nres;  // nres: residual rows per group (m when full_residual, else emax)
     int kp;           // position-table stride: round4 of the stage-A kernel's K (a compiled K > k
                       // codes k, sh::fixed_kernel_k; the entries past k stay 0xFF)
     int *e;
@@ -601,32 +601,19 @@ struct DecodeWS {
     long long coefA_gs, coefB_gs;
 };
 
-// Stage B after a full-residual stage A: stageb_v2 for emax > 8, where it measured faster
-// ((200,32) e = 32: 0.34 vs 0.39 ms; (200,56) e = 56: 0.478 vs 0.532 ms; (190,66) e = 66: 0.763 vs
-// 0.838 ms and (120,136) e = 120: 1.77 vs 2.07 ms against stageb_fixed, with 4- or 8-wave chunks;
-// C2 (64,16) e = 16: 0.229 vs 0.280 ms and (112,16) 0.142 vs 0.177 ms against stageb_regs, with
-// 2-wave workgroups and an 8-row ring, stageb.hip); round 2's stageb_regs with setup-written
-// snippet addresses for emax <= 8 ((28,4,1400) 0.114 vs 0.132 ms for a one-wave v2).
-// SH_STAGEB_OLD=1 (measurement switch) selects round 2's kernels everywhere; SH_V2_MIN / SH_V2_MAX
-// bound the emax served by stageb_v2.
-bool stageb_v2_on(const sh::Geometry &geo, int emax) {
-    static const bool old = SH_MEASURE_ENV("SH_STAGEB_OLD") != nullptr;
-    static const int vmax = sh::measure_int(SH_MEASURE_ENV("SH_V2_MAX"), 128);  // measurement
-    static const int vmin = sh::measure_int(SH_MEASURE_ENV("SH_V2_MIN"), 8);    // measurement
-    return !old && emax > vmin && emax <= vmax && sh::stageb_v2_ok(geo, emax);
-}
-
 size_t carve(DecodeWS &w, uint8_t *base, int k, int m, int B, int groups, bool need_recovered) {
     const sh::Geometry geo = sh::fixed_geometry(B);
     w.emax = std::min(k, m);
-    // stage A over all m rows (compile-time or tile kernels), position tables, snippet stage B
-    w.fixed = (sh::has_fixed(k, m, B) || tile_usable(ctx(), k, m, B)) && sh::stageb_fixed_ok(geo, w.emax);
+    // stage A over all m rows (compile-time or tile kernels) and position tables, where the
+    // geometry lets a residual stage-B kernel follow
+    w.route = sh::stageb_route(geo, w.emax, sh::has_fixed(k, m, B) || tile_usable(ctx(), k, m, B));
+    w.full_residual = w.route != sh::StageBRoute::Snip;
+    const bool regs = w.route == sh::StageBRoute::Regs;
     const int kfix = force_tile() ? 0 : sh::fixed_kernel_k(k, m, B);
     w.kp = round4(std::max(k, kfix));
-    w.small = w.fixed && sh::stageb_small_ok(geo, w.emax);
-    w.ldA = w.fixed ? 0 : round4(k);
+    w.ldA = w.full_residual ? 0 : round4(k);
     w.ldB = (w.emax + 7) & ~7;  // stage-B coefficients [i][ldB] (transposed, 8-entry rows)
-    w.nres = w.fixed ? m : w.emax;
+    w.nres = w.full_residual ? m : w.emax;
     w.coefA_gs = static_cast<long long>(w.emax) * w.ldA;
     w.coefB_gs = static_cast<long long>(w.emax) * w.ldB;
     size_t off = 0;
@@ -639,15 +626,13 @@ size_t carve(DecodeWS &w, uint8_t *base, int k, int m, int B, int groups, bool n
     w.e = reinterpret_cast<int *>(take(G * sizeof(int)));
     w.rec_idx = take(G * w.emax);
     w.erasures = take(G * w.emax);
-    w.coefA = w.fixed ? nullptr : take(G * w.coefA_gs);
-    w.coefB = (w.fixed && !w.small && !stageb_v2_on(geo, w.emax)) ? nullptr : take(G * w.coefB_gs);
-    w.v2 = w.fixed && !w.small && stageb_v2_on(geo, w.emax);
-    w.targets = (w.fixed && !w.small && !w.v2)
-                    ? reinterpret_cast<uint64_t *>(take(G * w.emax * w.ldB * sizeof(uint64_t)))
-                    : nullptr;
-    w.rrow = w.fixed ? take(G * round4(w.emax)) : nullptr;
-    w.pos = w.fixed ? take(G * w.kp) : nullptr;
-    w.rpos = w.fixed ? take(G * round4(m)) : nullptr;
+    w.coefA = w.full_residual ? nullptr : take(G * w.coefA_gs);
+    // stage-B coefficients: snippet addresses for stageb_regs, bytes for every other kernel
+    w.coefB = regs ? nullptr : take(G * w.coefB_gs);
+    w.targets = regs ? reinterpret_cast<uint64_t *>(take(G * w.emax * w.ldB * sizeof(uint64_t))) : nullptr;
+    w.rrow = w.full_residual ? take(G * round4(w.emax)) : nullptr;
+    w.pos = w.full_residual ? take(G * w.kp) : nullptr;
+    w.rpos = w.full_residual ? take(G * round4(m)) : nullptr;
     w.residual = take(G * w.nres * static_cast<size_t>(B) + 256);  // + slack: word over-read
     w.recovered = need_recovered ? take(G * w.emax * static_cast<size_t>(B)) : nullptr;
     return off;
@@ -664,39 +649,43 @@ int stageb_row_slice() {
 // stageb_row_slice() rows, one workgroup each, whose partial outputs are XOR-reduced into dst.
 hipError_t launch_stage_b(const DecodeWS &w, int n_in, int B, int groups, uint8_t *dst, hipStream_t s,
                           uint8_t *slice_scratch = nullptr) {
-    if (w.small) {
-        sh::StageBSmallArgs f{};
-        f.in = w.residual;
-        f.in_gstride = static_cast<long long>(n_in) * B;
-        f.out = dst;
-        f.out_gstride = static_cast<long long>(w.emax) * B;
-        f.e = w.e;
-        f.rrow = w.rrow;
-        f.ldR = round4(w.emax);
-        f.coefT = w.coefB;
-        f.coefT_gstride = w.coefB_gs;
-        f.ldT = w.ldB;
-        f.emax = w.emax;
-        f.groups = groups;
-        f.geo = sh::fixed_geometry(B);
-        return sh::launch_stageb_small(f, s);
+    if (w.route == sh::StageBRoute::Snip) {
+        sh::StageBArgs b{};
+        b.in = w.residual;
+        b.in_gstride = static_cast<long long>(n_in) * B;
+        b.n_in = n_in;
+        b.out = dst;
+        b.out_gstride = static_cast<long long>(w.emax) * B;
+        b.e = w.e;
+        b.coefT = w.coefB;
+        b.coefT_gstride = w.coefB_gs;
+        b.ldT = w.ldB;
+        b.groups = groups;
+        b.geo = sh::make_geometry(B);
+        return sh::launch_stageb(b, w.emax, s);
     }
-    if (w.v2) {
-        sh::StageBV2Args f{};
-        f.in = w.residual;
-        f.in_gstride = static_cast<long long>(n_in) * B;
-        f.out = dst;
-        f.out_gstride = static_cast<long long>(w.emax) * B;
-        f.e = w.e;
-        f.rrow = w.rrow;
-        f.ldR = round4(w.emax);
-        f.coefT = w.coefB;
-        f.coefT_gstride = w.coefB_gs;
-        f.ldT = w.ldB;
-        f.emax = w.emax;
-        f.groups = groups;
-        f.geo = sh::fixed_geometry(B);
-        f.snip_base = ctx().snip_base;
+    sh::StageBResidualArgs f{};
+    f.in = w.residual;
+    f.in_gstride = static_cast<long long>(n_in) * B;
+    f.out = dst;
+    f.out_gstride = static_cast<long long>(w.emax) * B;
+    f.e = w.e;
+    f.rrow = w.rrow;
+    f.ldR = round4(w.emax);
+    f.coefT = w.coefB;
+    f.coefT_gstride = w.coefB_gs;
+    f.ldT = w.ldB;
+    f.emax = w.emax;
+    f.groups = groups;
+    f.geo = sh::fixed_geometry(B);
+    f.snip_base = ctx().snip_base;
+    f.targets = w.targets;
+    switch (w.route) {
+    case sh::StageBRoute::Small:
+        return sh::launch_stageb_small(f, s);
+    case sh::StageBRoute::Regs:
+        return sh::launch_stageb_regs(f, s);
+    default: {  // V2
         // at most kSliceCap partial outputs fit slice_scratch (a small measurement
         // setting of SH_SB_SLICE must not write past it)
         const int rs0 = stageb_row_slice();
@@ -711,35 +700,7 @@ hipError_t launch_stage_b(const DecodeWS &w, int n_in, int B, int groups, uint8_
         }
         return sh::launch_stageb_v2(f, s);
     }
-    if (w.fixed) {
-        sh::StageBFixedArgs f{};
-        f.in = w.residual;
-        f.in_gstride = static_cast<long long>(n_in) * B;
-        f.out = dst;
-        f.out_gstride = static_cast<long long>(w.emax) * B;
-        f.e = w.e;
-        f.rrow = w.rrow;
-        f.targets = w.targets;
-        f.emax = w.emax;
-        f.ldR = round4(w.emax);
-        f.ldT = w.ldB;
-        f.groups = groups;
-        f.geo = sh::fixed_geometry(B);
-        return sh::launch_stageb_fixed(f, s);
     }
-    sh::StageBArgs b{};
-    b.in = w.residual;
-    b.in_gstride = static_cast<long long>(n_in) * B;
-    b.n_in = n_in;
-    b.out = dst;
-    b.out_gstride = static_cast<long long>(w.emax) * B;
-    b.e = w.e;
-    b.coefT = w.coefB;
-    b.coefT_gstride = w.coefB_gs;
-    b.ldT = w.ldB;
-    b.groups = groups;
-    b.geo = sh::make_geometry(B);
-    return sh::launch_stageb(b, w.emax, s);
 }
 
 // Common decode core (m >= 2, valid params): writes recovered blocks densely into `dst`
@@ -803,7 +764,7 @@ int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_bl
     if (ev) SH_CHECK(hipEventRecord(ev[1], s));
 
     const Geometry geo = sh::make_geometry(B);
-    if (w.fixed) {
+    if (w.full_residual) {
         // Stage A (compile-time generator, all m rows, erased columns read as zeros):
         //   residual_y = R_y + sum_{received x} M(C[y][x]) d_x
         // (the tile kernels read position tables round4(k) wide: not after a wider compiled K)
@@ -868,7 +829,7 @@ int invalid_decode_status(int k, int groups, const uint8_t *d_rows, hipStream_t 
 // erased original row (sort_blocks order, cauchy_256.cpp:522-554), 0 < e <= number of erasures.
 bool host_decode_setup(const DecodeWS &w, int k, int m, const uint8_t *rows, int e, const int *rec,
                        const int *era) {
-    if (!w.fixed || !(w.v2 || w.small) || m < 7 || !w.coefB || !w.rrow || !w.pos || !w.rpos) return false;
+    if (!(w.route == sh::StageBRoute::V2 || w.route == sh::StageBRoute::Small) || m < 7 || !w.coefB || !w.rrow || !w.pos || !w.rpos) return false;
     const sh::GF256 &f = sh::gf();
     std::vector<uint8_t> xp, yp;
     sh::cauchy_params(k, m, xp, yp);

@@ -467,7 +467,7 @@ __global__ __launch_bounds__(64 * W, 8) void decode_setup(DecodeSetupArgs a, int
     // snippet of each coefficient (the null snippet for zeros and for outputs j >= e), plus the
     // residual row of each received recovery block.
     // Byte coefficients (generic path, and the small-block stage B after a compile-time stage A:
-    // targets == nullptr) or snippet addresses (stageb_fixed).
+    // targets == nullptr) or snippet addresses (stageb_regs).
     uint8_t *Bc = a.targets ? nullptr : a.coefB + static_cast<long long>(g) * a.coefB_gstride;
     // fixed layout [g][j / 8][i][j % 8]: one wave's 8 addresses of consecutive rows are contiguous
     uint64_t *Tg = a.targets ? a.targets + static_cast<long long>(g) * emax * a.ldB : nullptr;

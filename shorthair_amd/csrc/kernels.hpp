@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "geometry.hpp"
+#include "stageb_route.hpp"
 
 namespace sh {
 
@@ -100,71 +101,42 @@ struct StageBArgs {
 };
 hipError_t launch_stageb(const StageBArgs &a, int emax, hipStream_t stream);
 
-// Decode stage B, compile-time path: out[g][j] = sum_{i < e} M(S^-1[j][i]) in[g][rrow[g][i]]
-// with the coefficients given as snippet addresses (DecodeSetupArgs::targets).
-struct StageBFixedArgs {
-    const uint8_t *in;        // [G][n_in][B] residual rows (all m generator rows)
-    long long in_gstride;
-    uint8_t *out;             // [G][emax][B]
-    long long out_gstride;
-    const int *e;             // [G] received recovery blocks = outputs (<= 0: nothing to do)
-    const uint8_t *rrow;      // [G][ldR]
-    const uint64_t *targets;  // [G][ldT/8][emax][8], entry [j/8][i][j%8]
-    int emax;
-    int ldR;                  // round4(emax): row lists are read as dwords
-    int ldT;                  // multiple of 8
-    int groups;
-    Geometry geo;
-};
-bool stageb_fixed_ok(const Geometry &geo, int emax);
-hipError_t launch_stageb_fixed(const StageBFixedArgs &a, hipStream_t stream);
-// Decode stage B after a full-residual stage A (compile-time or tile kernels), byte coefficients:
-// out[g][j] = sum_{i < e} M(coefT[g][i][j]) in[g][rrow[g][i]] (csrc/stageb.hip, stageb_v2).
-struct StageBV2Args {
+// Decode stage B after a full-residual stage A (compile-time or tile kernels; csrc/stageb.hip):
+//   out[g][j] = sum_{i < e} M(S^-1[j][i]) in[g][rrow[g][i]]
+// One argument block for the three residual kernels; stageb_route (stageb_route.hpp) picks the
+// kernel, and with it which form of the coefficients the setup wrote: bytes (coefT; stageb_v2,
+// stageb_small) or snippet addresses (targets; stageb_regs). The fields up to out_slice_bytes are
+// in the order the headline kernel stageb_v2 has always read them.
+struct StageBResidualArgs {
     const uint8_t *in;        // [G][n_in][B] residual rows (all m generator rows)
     long long in_gstride;
     uint8_t *out;             // [G][emax][B]
     long long out_gstride;
     const int *e;             // [G] received recovery blocks = outputs (<= 0: nothing to do)
     const uint8_t *rrow;      // [G][ldR] residual row of the i-th received recovery block
-    int ldR;                  // round4(emax)
-    const uint8_t *coefT;     // [G][emax][ldT]: entry [i][j] = S^-1[j][i] (0 past e)
+    int ldR;                  // round4(emax): stageb_regs reads the row lists as dwords
+    const uint8_t *coefT;     // V2, Small: [G][emax][ldT], entry [i][j] = S^-1[j][i] (0 past e)
     long long coefT_gstride;
     int ldT;                  // multiple of 8
     int emax;
     int groups;
     Geometry geo;
-    uint64_t snip_base;       // address of snippet 0 of the accumulating table (stride SNIP_STRIDE)
-    int j_base;               // set by the launcher: first output of the launch (a tail launch)
-    // Row slices (single-group latency path; 0 = off): workgroup z applies input rows
+    uint64_t snip_base;       // V2: address of snippet 0 of the accumulating table (stride SNIP_STRIDE)
+    int j_base;               // V2, set by the launcher: first output of the launch (a tail launch)
+    // V2 row slices (single-group latency path; 0 = off): workgroup z applies input rows
     // [z * row_slice, min(e, (z + 1) * row_slice)) and writes its partial output at
     // out + z * out_slice_bytes; the caller XOR-reduces the partials.
     int row_slice;
     int row_slices;
     long long out_slice_bytes;
+    const uint64_t *targets;  // Regs: [G][ldT/8][emax][8], snippet address of S^-1[j][i] at [j/8][i][j%8]
+    int xcd_map;              // Small, set by the launcher: 1 = XCD-aware block order (see stageb_small)
 };
-bool stageb_v2_ok(const Geometry &geo, int emax);
-hipError_t launch_stageb_v2(const StageBV2Args &a, hipStream_t stream);
-// Decode stage B for small blocks after a compile-time stage A (csrc/stageb.hip, stageb_small):
-// per-lane coefficients, so one wave serves 64 / nq groups.
-struct StageBSmallArgs {
-    const uint8_t *in;        // [G][in_gstride] residual rows (all m generator rows)
-    long long in_gstride;
-    uint8_t *out;             // [G][out_gstride]
-    long long out_gstride;
-    const int *e;             // [G] received recovery blocks = outputs (<= 0: nothing to do)
-    const uint8_t *rrow;      // [G][ldR] residual row of the i-th received recovery block
-    int ldR;
-    const uint8_t *coefT;     // [G][emax][ldT]: entry [i][j] = S^-1[j][i] (0 past e)
-    long long coefT_gstride;
-    int ldT;                  // multiple of 8
-    int emax;
-    int groups;
-    Geometry geo;
-    int xcd_map;              // set by the launcher: 1 = XCD-aware block order (see stageb_small)
-};
-bool stageb_small_ok(const Geometry &geo, int emax);
-hipError_t launch_stageb_small(const StageBSmallArgs &a, hipStream_t stream);
+// Each launches its route's kernel; hipErrorNotSupported (nothing launched) when
+// stageb_route(a.geo, a.emax, true) is another route.
+hipError_t launch_stageb_regs(const StageBResidualArgs &a, hipStream_t stream);
+hipError_t launch_stageb_v2(const StageBResidualArgs &a, hipStream_t stream);
+hipError_t launch_stageb_small(const StageBResidualArgs &a, hipStream_t stream);
 // Address of stage-B snippet 0 in the loaded code object (one tiny kernel launch + copy).
 hipError_t stageb_snip_base(uint64_t *out_host, hipStream_t stream);
 constexpr int SNIP_STRIDE = 72;   // bytes per stage-B snippet (gen_fixed_kernels.py)

@@ -11,10 +11,13 @@
 // are emitted as code (csrc/gen/snippets.h); the kernel reaches snippet c with one s_swappc_b64
 // and the snippet returns with s_setpc_b64.
 //
-// Two kernels: stageb_snip (generic path, any geometry; copy-and-XOR snippets, coefficients as
-// bytes) and stageb_fixed (after a compile-time stage A: accumulating snippets in VGPR-index
-// mode, setup-computed snippet addresses, residual rows through a per-workgroup LDS-DMA ring). Group-uniform coefficients
-// require a wave to stay inside one group: at B = 1400 a group has 44 word columns.
+// Four kernels, one per route (stageb_route.hpp): stageb_snip (generic path, any geometry;
+// copy-and-XOR snippets, coefficients as bytes) and, after a stage A that leaves all m residual
+// rows, stageb_regs and stageb_v2 (accumulating snippets in VGPR-index mode; setup-written snippet
+// addresses and rows in registers for emax <= 8, byte coefficients and rows through a
+// per-workgroup LDS-DMA ring above) and stageb_small (B <= 512: per-lane coefficients applied by
+// LDS lookups). Group-uniform coefficients require a wave of the snippet kernels to stay inside one
+// group: at B = 1400 a group has 44 word columns.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -131,8 +134,8 @@ __global__ __launch_bounds__(256) void stageb_snip(StageBArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Compile-time path (after a generated stage-A kernel, csrc/gen/): one workgroup = one group x
-// one 64-column chunk x 32 outputs (4 waves x 8 outputs j0..j0+7).
+// Full-residual path (after a generated stage-A kernel, csrc/gen/, or the tile kernels), emax <= 8:
+// one workgroup = one group x one 64-column chunk x 32 outputs (4 waves x 8 outputs j0..j0+7).
 //
 //   out[j] = sum_{i < e} M(S^-1[j][i]) residual[rrow[i]]      (reference :1233-1392 semantics)
 //
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(256) void stageb_snip(StageBArgs a) {
 // (compacted: only the e rows that exist are staged and visited, so the work scales with e^2)
 // and, for every (i, j), the ABSOLUTE address of the snippet that applies M(S^-1[j][i])
 // (snippet 256 = return at once for zero / unused entries). The row loop therefore does no
-// scalar address arithmetic: per input row it takes the 8 sub-block words (from the ring), builds the
+// scalar address arithmetic: per input row it takes the 8 sub-block words, builds the
 // two 4-bit window tables (reference win_encode tables, cauchy_256.cpp:1426-1445, 22 XORs) into
 // the pinned registers v[96:127], and makes 8 calls into the snippet table in VGPR-index mode
 // (accumulator set j at v[32+8j..]).
@@ -235,11 +238,12 @@ __device__ __forceinline__ void row_regs(const Row8 &d, const uint64_t (&tg)[8],
                    "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "s40", "s41", "m0", "memory");
 }
 
-// Small e (emax <= 16): the waves load their own rows, two rows ahead into registers, with no
-// barrier. A workgroup ring would keep four waves resident per group for e <= 8 and spend its
-// 12-row prologue on rows that do not exist (C4 (28,4,1400) decode 0.66 vs 0.55 ms, C2 0.83 vs
-// 0.76 ms), while with e = 32 the shared ring wins (below).
-__global__ __launch_bounds__(256, 4) void stageb_regs(StageBFixedArgs a) {
+// The waves load their own rows, two rows ahead into registers, with no barrier. A four-wave
+// workgroup ring would keep four waves resident per group for e <= 8 and spend its 12-row
+// prologue on rows that do not exist (C4 (28,4,1400) decode 0.66 vs 0.55 ms); a one-wave
+// stageb_v2 with its 8-row ring loses too (0.132 vs 0.114 ms). From emax = 9 on the shared ring of
+// stageb_v2 wins (C2 (64,16): 0.229 vs 0.280 ms) and stageb_route sends the shape there.
+__global__ __launch_bounds__(256, 4) void stageb_regs(StageBResidualArgs a) {
     const Geometry geo = a.geo;
     const int ncc = (geo.nq + 63) / 64;
     const int g = blockIdx.x / ncc;
@@ -337,116 +341,23 @@ __global__ __launch_bounds__(256, 4) void stageb_regs(StageBFixedArgs a) {
     }
 }
 
-// The residual rows are staged in one LDS ring per workgroup (one group, 64-column
-// chunk): each row is fetched ONCE per workgroup by LDS-DMA (2 KB: waves 0 and 1 issue one 1 KB
-// piece each) instead of once per wave, with up to 12 rows in flight per workgroup. Rows in groups
-// of RB_S: before a group every wave waits for its own DMAs of it (counted vmcnt, constant in the
-// steady state) and joins the barrier, which also frees the slots of the previous group; they are
-// refilled right there. Waves without outputs (8 * wave >= e) join the barriers and compute nothing.
-// Measured at the headline (8192 groups, e = 32): 0.360 vs 0.377-0.384 ms for waves that each
-// loaded their own rows two rows ahead into registers (round 2's form; an LDS tile of the whole
-// residual loaded up front, 48 KB per workgroup, took 0.42 ms).
-constexpr int RB_R = 16, RB_S = 4, RB_ROW = 8 * 64 * 4;
-static_assert(RB_R == 4 * RB_S, "steady state: the slots of one group are refilled per group");
-
-__global__ __launch_bounds__(256, 4) void stageb_fixed(StageBFixedArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t ring[RB_R * RB_ROW];
-    const Geometry geo = a.geo;
-    const int ncc = (geo.nq + 63) / 64;
-    const int g = blockIdx.x / ncc;
-    const int cc = blockIdx.x - g * ncc;
-    const int c0 = cc * 64;
-    const int ncols = min(64, geo.nq - c0);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int e = a.e[g];
-    if (e <= 0) return;  // uniform over the workgroup
-    const int j0 = (blockIdx.y * 4 + wave) * 8;
-    const bool active = j0 < e;
-    const long long gbase = static_cast<long long>(g) * a.in_gstride;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t *>(a.in + gbase), static_cast<short>(0), static_cast<int>(a.in_gstride), 0x00020000);
-    // DMA piece of waves 0 and 1: slot bytes [wave*1024 + lane*16, +16) = sub-block sa, columns
-    // c0 + cq .. + 3 (a whole 4-column chunk: nq % 4 == 0); chunks past the group read zeros
-    const int off = wave * 1024 + lane * 16;
-    const int sa = off / 256, cq = (off % 256) / 4;
-    const uint32_t dsrc = (c0 + cq < geo.nq) ? colx_off(c0 + cq, geo.nq, geo.sub) + static_cast<uint32_t>(sa * geo.sub)
-                                             : 0x80000000u;
-    typedef const __attribute__((address_space(4))) uint32_t cu32_t;
-    typedef const __attribute__((address_space(4))) uint64_t cu64_t;
-    const cu32_t *rr = (const cu32_t *)(a.rrow + static_cast<long long>(g) * a.ldR);
-    const cu64_t *tp = (const cu64_t *)(a.targets + (static_cast<long long>(g) * (a.ldT / 8) + (j0 >> 3)) * a.emax * 8);
-    const int elast = e - 1;
-    // Row i into slot i % RB_R. Rows past the end are issued too (the counted waits stay
-    // constant) but out of range: no memory access, zeros into a slot nobody reads (it held a
-    // row of the previous group, which every wave has finished).
-    auto issue = [&](int i) {
-        if (wave < 2) {
-            const int x = min(i, elast);
-            const uint32_t soff = ((rr[x >> 2] >> (8 * (x & 3))) & 0xFFu) * static_cast<uint32_t>(geo.B);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(ring + (i % RB_R) * RB_ROW + wave * 1024),
-                                                     16, i < e ? dsrc : 0x80000000u, soff, 0, 0);
-        }
-    };
-    u32x16 a01, a23, a45, a67;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) a01[t] = a23[t] = a45[t] = a67[t] = 0;
-    uint32_t z0 = 0, z1 = 0;
-    for (int i = 0; i < RB_R - RB_S; ++i) issue(i);
-    const int ngroups = (e + RB_S - 1) / RB_S;
-    for (int ig = 0; ig < ngroups; ++ig) {
-        // own DMAs of rows 4ig..4ig+3 landed (RB_R - 2 * RB_S younger ones may be outstanding)
-        if (wave < 2)
-            asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(RB_R - 2 * RB_S) : "memory");
-        else
-            asm volatile("s_barrier" ::: "memory");
-#pragma unroll
-        for (int r = 0; r < RB_S; ++r) issue(ig * RB_S + RB_R - RB_S + r);
-        if (!active) continue;
-#pragma unroll
-        for (int r = 0; r < RB_S; ++r) {
-            const int i = ig * RB_S + r;
-            if (i >= e) break;  // uniform
-            uint64_t tg[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) tg[j] = tp[i * 8 + j];
-            const uint8_t *slot = ring + (i % RB_R) * RB_ROW + lane * 4;
-            Row8 d;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) d.w[s] = *reinterpret_cast<const uint32_t *>(slot + s * 256);
-            row_regs(d, tg, a01, a23, a45, a67, z0, z1);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no ring DMA may land after the workgroup ends
-    if (!active || lane >= ncols) return;
-    uint32_t acc[8][8];
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        acc[0][b] = a01[b]; acc[1][b] = a01[8 + b];
-        acc[2][b] = a23[b]; acc[3][b] = a23[8 + b];
-        acc[4][b] = a45[b]; acc[5][b] = a45[8 + b];
-        acc[6][b] = a67[b]; acc[7][b] = a67[8 + b];
-    }
-    uint8_t *out = a.out + static_cast<long long>(g) * a.out_gstride + colx_off(c0 + lane, geo.nq, geo.sub);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if (j0 + j >= e) break;
-        uint8_t *row = out + static_cast<long long>(j0 + j) * geo.B;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) __builtin_memcpy(row + b * geo.sub, &acc[j][b], 4);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // stageb_v2: one workgroup = one group x one 64-column chunk x up to 8*NW outputs (NW waves of 8),
 // so for e <= 8*NW every residual row is fetched ONCE per (group, chunk) however large e is
-// (stageb_fixed re-streamed all e rows per 32 outputs: e = 56..66 at the Tester's shapes).
+// (a 4-wave workgroup per 32 outputs re-streamed all e rows: e = 56..66 at the Tester's shapes).
 // Per row a wave needs the snippet addresses of its 8 coefficients S^-1[j0..j0+7][i]; they come
 // from the byte coefficients (setup's transposed [i][j] table), copied once per workgroup into
 // LDS ([wave][row], 8 bytes each), read one row ahead with the row's words (one ds_read_b64 at a
 // wave-uniform address, two v_readfirstlane) and turned into addresses base + 72*c by SALU. The
 // rows' scalar loads of round 2 (one 64-byte s_load of addresses per row, first touch of
 // 64 MB written by the setup) exposed a memory latency on every row.
+//
+// The residual rows are staged in one LDS ring per workgroup: each row is fetched ONCE per
+// workgroup by LDS-DMA (2 KB: waves 0 and 1 issue one 1 KB piece each) instead of once per wave,
+// with up to 12 rows in flight. Rows in groups of RB_S: before a group every wave waits for its
+// own DMAs of it (counted vmcnt, constant in the steady state) and joins the barrier, which also
+// frees the slots of the previous group; they are refilled right there. Waves without outputs
+// (j0 >= e) join the barriers and compute nothing.
 // ---------------------------------------------------------------------------------------------
 #define SH_V2_STEP_ASM                                                                            \
     "v_mov_b32 v97, %[d0]\n"                                                                      \
@@ -539,15 +450,16 @@ __device__ __forceinline__ void v2_row(const Row8 &d, uint32_t c0, uint32_t c1, 
 }
 
 constexpr int V2_MAXE = 128;  // emax = min(k, m) <= 128 whenever k + m <= 256
+constexpr int RING_ROW = 8 * 64 * 4;  // bytes of a ring row: 8 sub-block words of 64 columns
 
 // Ring depth: 16 rows (4 per barrier group) for 4- and 8-wave workgroups; 8 rows (2 per group)
 // for the 1- and 2-wave workgroups of emax <= 16, so their 16 KB rings let 9 of them share a CU.
 // MAXE: the rows a wave's coefficient copy holds (16 for the 1-2-wave workgroups of emax <= 16;
 // V2_MAXE for the others, and for the 1-2-wave tail launches of a larger emax).
 template <int NW, int MAXE = (NW <= 2 ? 16 : V2_MAXE)>
-__global__ __launch_bounds__(64 * NW) void stageb_v2(StageBV2Args a) {
+__global__ __launch_bounds__(64 * NW) void stageb_v2(StageBResidualArgs a) {
     constexpr int RB_R = NW <= 2 ? 8 : 16, RB_S = RB_R / 4;
-    __shared__ __attribute__((aligned(16))) uint8_t ring[RB_R * RB_ROW];
+    __shared__ __attribute__((aligned(16))) uint8_t ring[RB_R * RING_ROW];
     __shared__ __attribute__((aligned(8))) uint32_t cf[NW][MAXE][2];  // [wave][row] coefficient bytes
     const Geometry geo = a.geo;
     const int ncc = (geo.nq + 63) / 64;
@@ -602,7 +514,7 @@ __global__ __launch_bounds__(64 * NW) void stageb_v2(StageBV2Args a) {
             const int x = min(i0 + i, elast);
             const uint32_t w = __builtin_amdgcn_readlane(rrv, x >> 2);
             const uint32_t soff = ((w >> (8 * (x & 3))) & 0xFFu) * static_cast<uint32_t>(geo.B);
-            uint8_t *dst = ring + (i % RB_R) * RB_ROW + wave * 1024;
+            uint8_t *dst = ring + (i % RB_R) * RING_ROW + wave * 1024;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)dst, 16,
                                                      i < nr ? dsrc : 0x80000000u, soff, 0, 0);
             if (NW == 1)
@@ -636,7 +548,7 @@ __global__ __launch_bounds__(64 * NW) void stageb_v2(StageBV2Args a) {
         for (int r = 0; r < RB_S; ++r) {
             const int i = ig * RB_S + r;
             if (i >= nr) break;  // uniform
-            const uint8_t *slot = ring + (i % RB_R) * RB_ROW + lane * 4;
+            const uint8_t *slot = ring + (i % RB_R) * RING_ROW + lane * 4;
             Row8 d;
 #pragma unroll
             for (int s = 0; s < 8; ++s) d.w[s] = *reinterpret_cast<const uint32_t *>(slot + s * 256);
@@ -666,13 +578,9 @@ __global__ __launch_bounds__(64 * NW) void stageb_v2(StageBV2Args a) {
     }
 }
 
-bool stageb_v2_ok(const Geometry &geo, int emax) {
-    return geo.nq % 4 == 0 && geo.sub >= 16 && emax >= 1 && emax <= V2_MAXE;
-}
-
-hipError_t launch_stageb_v2(const StageBV2Args &a, hipStream_t stream) {
+hipError_t launch_stageb_v2(const StageBResidualArgs &a, hipStream_t stream) {
     if (a.groups <= 0 || a.emax <= 0) return hipSuccess;
-    if (!stageb_v2_ok(a.geo, a.emax)) return hipErrorNotSupported;
+    if (stageb_route(a.geo, a.emax, true) != StageBRoute::V2 || a.emax > V2_MAXE) return hipErrorNotSupported;
     const int ncc = (a.geo.nq + 63) / 64;
     const int octets = (a.emax + 7) / 8;
     // Output chunks of 4 or 8 waves (32 or 64 outputs) per workgroup: a wave count that is not a
@@ -680,7 +588,7 @@ hipError_t launch_stageb_v2(const StageBV2Args &a, hipStream_t stream) {
     // measured 10 % slower at e = 56, 66). Each chunk streams all e rows, so 8-wave chunks unless
     // 4-wave chunks need fewer wave slots (e = 66: 3 x 4 waves, 9 active, vs 2 x 8 with 7 idle):
     // (200,56,1352) stage B 0.478 vs 0.532 ms (7 waves), (190,66,1336) 0.763 vs 0.838 ms
-    // (stageb_fixed), (120,136,1400) 1.772 vs 2.070 ms (4096 groups).
+    // (the retired 4-wave LDS-ring kernel), (120,136,1400) 1.772 vs 2.070 ms (4096 groups).
     // One or two output octets (emax <= 16): one workgroup of as many waves, no idle waves.
     static const int force = sh::measure_int(SH_MEASURE_ENV("SH_V2_NW"), 0);  // measurement
     const int c4 = (octets + 3) / 4, c8 = (octets + 7) / 8;
@@ -697,7 +605,7 @@ hipError_t launch_stageb_v2(const StageBV2Args &a, hipStream_t stream) {
     const int rem = octets - (chunks - 1) * nw1;  // octets of the last chunk
     const bool tail = !no_tail && chunks > 1 && rem <= 2 && nw1 >= 4;
     if (tail) --chunks;
-    StageBV2Args m = a;
+    StageBResidualArgs m = a;
     m.j_base = 0;
     const unsigned zs = a.row_slice > 0 ? static_cast<unsigned>(a.row_slices) : 1u;
     dim3 grid(static_cast<unsigned>(ncc) * a.groups, chunks, zs);
@@ -721,144 +629,28 @@ hipError_t launch_stageb_v2(const StageBV2Args &a, hipStream_t stream) {
 }
 
 // Decode stage B for small blocks (fixed geometry with nq <= 16 word columns, B <= 512). A
-// group fills only nq lanes there, and a snippet's coefficient is wave-uniform, so stageb_fixed
-// would leave 64 - nq lanes idle; here each lane applies its own group's coefficients instead and
-// one wave serves 64 / nq groups. Per residual row every lane writes its 30 window-table entries
-// (the reference's win_encode tables, cauchy_256.cpp:1426-1445, of its column's 8 words) to LDS
-// laid out [entry][lane]; coefficient c is applied as 8 x (two table lookups + one XOR3) with the
-// 16 entry indices of c (lo and 16 + hi of c * 2^b) read from a 256 x 16-byte table, each lookup
-// address one v_perm_b32 (entry into byte 1, lane * 4 into byte 0) and one ds_read_b32. One wave
-// per workgroup, so the table base is a compile-time offset.
-bool stageb_small_ok(const Geometry &geo, int emax) {
-    return geo.nq % 4 == 0 && geo.nq <= 16 && geo.sub >= 16 && emax >= 1 && emax <= 128;
-}
-
-__global__ __launch_bounds__(64) void stageb_small(StageBSmallArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t tab[32 * 64];  // 8 KB window tables [entry][lane]
-    __shared__ __attribute__((aligned(16))) uint32_t rbt[256 * 4];  // entry bytes of c * 2^b, b = 0..7
-    extern __shared__ uint8_t rrs[];  // row lists of the wave's groups, [gpw][emax] (launch-sized:
-                                      // 2 KB fixed kept 11 workgroups per CU instead of 13)
-    const Geometry geo = a.geo;
-    const int lane = threadIdx.x;
-    const int gpw = 64 / geo.nq;
-    const int gs = lane / geo.nq, q = lane - gs * geo.nq;
-    // Block order: every output chunk of a group block streams the same e residual rows, so the
-    // chunks of one group block are dealt to one XCD back to back (block b -> XCD b % 8) and the
-    // later ones read the rows from that XCD's L2; in chunk-major order ((224,32,256): 4 chunks)
-    // each chunk fetched them from memory again (4.5x the rows' bytes, PMC).
-    int gb = blockIdx.x, chunk = blockIdx.y;
-    if (a.xcd_map) {
-        const int nch = (a.emax + 7) / 8;
-        const int i = static_cast<int>(blockIdx.x) >> 3;
-        chunk = i % nch;
-        gb = (i / nch) * 8 + (static_cast<int>(blockIdx.x) & 7);
-        if (gb * gpw >= a.groups) return;  // padding blocks of the last XCD round
-    }
-    const int g0 = gb * gpw;
-    const bool valid = gs < gpw && g0 + gs < a.groups;
-    const int g = valid ? g0 + gs : g0;
-    const int j0 = chunk * 8;
-    for (int c = lane; c < 256; c += 64) {
-        uint32_t w[4] = {0, 0, 0, 0};
-        uint32_t v = static_cast<uint32_t>(c);
-        for (int b = 0; b < 8; ++b) {
-            w[b >> 1] |= ((v & 15u) | ((16u + (v >> 4)) << 8)) << (16 * (b & 1));
-            v = (v << 1) ^ ((v & 0x80u) ? 0x187u : 0u);  // c * 2^b in GF(256)/0x187
-        }
-        for (int t = 0; t < 4; ++t) rbt[c * 4 + t] = w[t];
-    }
-    tab[lane] = 0;            // T0[0]
-    tab[16 * 64 + lane] = 0;  // T1[0]
-    for (int t = lane; t < gpw * a.emax; t += 64) {
-        const int sl = t / a.emax, i = t - sl * a.emax;
-        const int gg = g0 + sl;
-        rrs[sl * a.emax + i] = (gg < a.groups && i < a.e[gg]) ? a.rrow[static_cast<long long>(gg) * a.ldR + i] : 0;
-    }
-    __syncthreads();
-    const int el = valid ? max(a.e[g], 0) : 0;
-    int emx = el;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) emx = max(emx, __shfl_xor(emx, o));
-    emx = __builtin_amdgcn_readfirstlane(emx);
-    if (emx <= j0) return;  // no lane has an output in this chunk
-
-    const uint8_t *res = a.in + static_cast<long long>(g) * a.in_gstride + colx_off(q, geo.nq, geo.sub);
-    const uint8_t *cp = a.coefT + static_cast<long long>(g) * a.coefT_gstride + j0;
-    const uint32_t lane4 = static_cast<uint32_t>(lane) * 4u;
-    auto load = [&](int i, uint32_t (&d)[8], uint64_t &cc) {
-        // lanes past the wave's last group (gs >= gpw, or past the batch) read row 0 of group g0:
-        // their rrs row was never written, and any other row could lie past the workspace
-        const int r = valid ? rrs[gs * a.emax + min(i, max(el - 1, 0))] : 0;
-        const uint8_t *p = res + static_cast<long long>(r) * geo.B;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) __builtin_memcpy(&d[s], p + s * geo.sub, 4);
-        cc = 0;
-        if (i < el) __builtin_memcpy(&cc, cp + static_cast<long long>(i) * a.ldT, 8);
-    };
-    auto lk = [&](uint32_t addr) { return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(tab) + addr); };
-
-    uint32_t acc[8][8];
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[jj][b] = 0;
-    uint32_t d[8], dn[8];
-    uint64_t cc, ccn;
-    load(0, d, cc);
-    for (int i = 0; i < emx; ++i) {
-        if (i + 1 < emx) load(i + 1, dn, ccn);  // next row in flight under this row's work
-        // window tables of this row's words: T0 from d0..d3, T1 from d4..d7
-        const uint32_t e3 = d[0] ^ d[1], e5 = d[0] ^ d[2], e6 = d[1] ^ d[2], e9 = d[0] ^ d[3];
-        const uint32_t e10 = d[1] ^ d[3], e12 = d[2] ^ d[3], e7 = e3 ^ d[2];
-        const uint32_t f3 = d[4] ^ d[5], f5 = d[4] ^ d[6], f6 = d[5] ^ d[6], f9 = d[4] ^ d[7];
-        const uint32_t f10 = d[5] ^ d[7], f12 = d[6] ^ d[7], f7 = f3 ^ d[6];
-        const uint32_t tv[32] = {0, d[0], d[1], e3, d[2], e5, e6, e7, d[3], e9, e10, e3 ^ d[3], e12, e5 ^ d[3], e6 ^ d[3], e7 ^ d[3],
-                                 0, d[4], d[5], f3, d[6], f5, f6, f7, d[7], f9, f10, f3 ^ d[7], f12, f5 ^ d[7], f6 ^ d[7], f7 ^ d[7]};
-#pragma unroll
-        for (int t = 1; t < 32; ++t)
-            if (t != 16) tab[t * 64 + lane] = tv[t];
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-            const uint32_t c = static_cast<uint32_t>(cc >> (8 * jj)) & 0xFFu;
-            const u32x4 rb = *reinterpret_cast<const u32x4 *>(&rbt[c * 4]);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const uint32_t w = rb[b >> 1];
-                const uint32_t k = 2u * (b & 1);  // byte k: T0 entry, byte k + 1: T1 entry
-                const uint32_t a0 = __builtin_amdgcn_perm(w, lane4, 0x0C0C0000u | ((4u + k) << 8));
-                const uint32_t a1 = __builtin_amdgcn_perm(w, lane4, 0x0C0C0000u | ((5u + k) << 8));
-                acc[jj][b] = __builtin_amdgcn_bitop3_b32(acc[jj][b], lk(a0), lk(a1), 0x96);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int s = 0; s < 8; ++s) d[s] = dn[s];
-        cc = ccn;
-    }
-    if (!valid) return;
-    uint8_t *out = a.out + static_cast<long long>(g) * a.out_gstride + colx_off(q, geo.nq, geo.sub);
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) {
-        if (j0 + jj >= el) break;
-        uint8_t *row = out + static_cast<long long>(j0 + jj) * geo.B;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) __builtin_memcpy(row + b * geo.sub, &acc[jj][b], 4);
-    }
-}
-
-// Two word columns per lane (stageb_small2): the two columns of a lane belong to one group, so
-// both take the same table entry for a coefficient and one ds_read_b64 fetches the pair — the
-// LDS array serves 8-byte reads at twice the 4-byte rate (MI355X_MICROARCH.md §LDS: ~150 vs
-// ~75 TB/s chip-wide), and the lookups are most of stageb_small's LDS time. Table layout
-// [half][entry][lane & 31] of uint2 (half = lane >> 5, 8 KB each), so an address is still one
-// v_perm_b32: entry + 32 * half in byte 1 (pre-added in the half's copy of the entry table) and
-// (lane & 31) * 8 in byte 0. Per launch at (224,32,256) (PMC, ab_runs block 10): LDS instructions
-// 6.4e7 -> 3.2e7, VALU 1.14e8 -> 7.8e7; with 24 KB of LDS and 212 VGPRs a CU holds 6 of these
-// waves (11-13 of stageb_small's), so the stage gains 7 %, not the halved lookup time.
+// group fills only nq lanes there, and a snippet's coefficient is wave-uniform, so the snippet
+// kernels would leave 64 - nq lanes idle; here each lane applies its own group's coefficients to
+// two word columns of that group and one wave serves 128 / nq groups. Per residual row every lane
+// writes its 30 window-table entries (the reference's win_encode tables, cauchy_256.cpp:1426-1445,
+// of its columns' 8 words) to LDS laid out [half][entry][lane & 31] of uint2 (half = lane >> 5,
+// 8 KB each); coefficient c is applied as 8 x (two table lookups + two XOR3) with the 16 entry
+// indices of c (lo and 16 + hi of c * 2^b) read from the 256 x 16-byte table rbt (one copy per
+// half, 32 * half pre-added), each lookup address one v_perm_b32 (entry into byte 1,
+// (lane & 31) * 8 into byte 0) and one ds_read_b64: both columns take the same entry, and the LDS
+// array serves 8-byte reads at twice the 4-byte rate. One wave per workgroup, so the table base is
+// a compile-time offset; the row lists of the wave's groups are in launch-sized LDS ([gpw][emax]:
+// 2 KB fixed cost two workgroups per CU).
+// Block order (xcd_map): every output chunk of a group block streams the same e residual rows, so
+// the chunks of one group block are dealt to one XCD back to back (block b -> XCD b % 8) and the
+// later ones read the rows from that XCD's L2; in chunk-major order ((224,32,256): 4 chunks) each
+// chunk fetched them from memory again (4.5x the rows' bytes, PMC).
+// Two columns per lane against one (ab_runs block 10): LDS instructions 6.4e7 -> 3.2e7 and VALU
+// 1.14e8 -> 7.8e7 per launch at (224,32,256), but 24 KB of LDS and 212 VGPRs leave 6 waves per CU,
+// so the stage gains 7 % (0.410 -> 0.380 ms; (112,16,256) -2 %, (28,4,256) equal).
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-__global__ __launch_bounds__(64) void stageb_small2(StageBSmallArgs a) {
+__global__ __launch_bounds__(64) void stageb_small(StageBResidualArgs a) {
     __shared__ __attribute__((aligned(16))) u32x2 tab[2 * 32 * 32];        // 16 KB window tables
     __shared__ __attribute__((aligned(16))) uint32_t rbt[2 * 256 * 4];     // entry bytes per half
     extern __shared__ uint8_t rrs[];
@@ -868,12 +660,12 @@ __global__ __launch_bounds__(64) void stageb_small2(StageBSmallArgs a) {
     const int gpw = 64 / lpg;
     const int gs = lane / lpg, ql = lane - gs * lpg;
     int gb = blockIdx.x, chunk = blockIdx.y;
-    if (a.xcd_map) {  // as stageb_small: the chunks of one group block on one XCD, back to back
+    if (a.xcd_map) {
         const int nch = (a.emax + 7) / 8;
         const int i = static_cast<int>(blockIdx.x) >> 3;
         chunk = i % nch;
         gb = (i / nch) * 8 + (static_cast<int>(blockIdx.x) & 7);
-        if (gb * gpw >= a.groups) return;
+        if (gb * gpw >= a.groups) return;  // padding blocks of the last XCD round
     }
     const int g0 = gb * gpw;
     const bool valid = gs < gpw && g0 + gs < a.groups;
@@ -914,6 +706,8 @@ __global__ __launch_bounds__(64) void stageb_small2(StageBSmallArgs a) {
     const uint32_t lane8 = static_cast<uint32_t>(lane & 31) * 8u;
     const uint32_t *rbh = rbt + half * 256 * 4;
     auto load = [&](int i, u32x2 (&d)[8], uint64_t &cc) {
+        // lanes past the wave's last group (gs >= gpw, or past the batch) read row 0 of group g0:
+        // their rrs row was never written, and any other row could lie past the workspace
         const int r = valid ? rrs[gs * a.emax + min(i, max(el - 1, 0))] : 0;
         const uint8_t *p = res + static_cast<long long>(r) * geo.B;
 #pragma unroll
@@ -975,26 +769,14 @@ __global__ __launch_bounds__(64) void stageb_small2(StageBSmallArgs a) {
     }
 }
 
-hipError_t launch_stageb_small(const StageBSmallArgs &a, hipStream_t stream) {
+hipError_t launch_stageb_small(const StageBResidualArgs &a, hipStream_t stream) {
     if (a.groups <= 0 || a.emax <= 0) return hipSuccess;
-    if (!stageb_small_ok(a.geo, a.emax)) return hipErrorNotSupported;
-    const int gpw = 64 / a.geo.nq;
+    if (stageb_route(a.geo, a.emax, true) != StageBRoute::Small) return hipErrorNotSupported;
+    const int gpw = 64 / (a.geo.nq / 2);  // two word columns per lane
     const int ngb = (a.groups + gpw - 1) / gpw, nch = (a.emax + 7) / 8;
     static const bool xcd = sh::measure_int(SH_MEASURE_ENV("SH_SMALL_XCD"), 1) != 0;  // measurement
-    StageBSmallArgs m = a;
+    StageBResidualArgs m = a;
     m.xcd_map = xcd && nch > 1 ? 1 : 0;
-    // Two word columns per lane (stageb_small2, ab_runs block 10: (224,32,256) 0.410 -> 0.380 ms,
-    // (112,16,256) -2 %, (28,4,256) equal); measurement builds: SH_SMALL2=0 runs stageb_small.
-    static const bool two = sh::measure_int(SH_MEASURE_ENV("SH_SMALL2"), 1) != 0;
-    if (two) {
-        const int gpw2 = 64 / (a.geo.nq / 2);
-        const int ngb2 = (a.groups + gpw2 - 1) / gpw2;
-        const dim3 grid2 = m.xcd_map ? dim3(static_cast<unsigned>(8 * nch * ((ngb2 + 7) / 8)), 1, 1)
-                                     : dim3(static_cast<unsigned>(ngb2), static_cast<unsigned>(nch), 1);
-        const size_t rrs2 = (static_cast<size_t>(gpw2) * a.emax + 15) & ~static_cast<size_t>(15);
-        hipLaunchKernelGGL(stageb_small2, grid2, dim3(64), rrs2, stream, m);
-        return hipGetLastError();
-    }
     const dim3 grid = m.xcd_map ? dim3(static_cast<unsigned>(8 * nch * ((ngb + 7) / 8)), 1, 1)
                                 : dim3(static_cast<unsigned>(ngb), static_cast<unsigned>(nch), 1);
     const size_t rrs_bytes = (static_cast<size_t>(gpw) * a.emax + 15) & ~static_cast<size_t>(15);
@@ -1002,20 +784,12 @@ hipError_t launch_stageb_small(const StageBSmallArgs &a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-bool stageb_fixed_ok(const Geometry &geo, int emax) {
-    // whole 4-column chunks (fixed_geometry) and one snippet accumulator set per output
-    return geo.nq % 4 == 0 && geo.sub >= 16 && emax >= 1;
-}
-
-hipError_t launch_stageb_fixed(const StageBFixedArgs &a, hipStream_t stream) {
+hipError_t launch_stageb_regs(const StageBResidualArgs &a, hipStream_t stream) {
     if (a.groups <= 0 || a.emax <= 0) return hipSuccess;
-    if (!stageb_fixed_ok(a.geo, a.emax)) return hipErrorNotSupported;
+    if (stageb_route(a.geo, a.emax, true) != StageBRoute::Regs) return hipErrorNotSupported;
     const int ncc = (a.geo.nq + 63) / 64;
     dim3 grid(static_cast<unsigned>(ncc) * a.groups, (a.emax + 31) / 32, 1);
-    if (a.emax <= 16)
-        hipLaunchKernelGGL(stageb_regs, grid, dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(stageb_fixed, grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(stageb_regs, grid, dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

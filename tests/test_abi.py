@@ -171,3 +171,47 @@ def test_package_before_torch_shares_one_hip_runtime():
             "assert x.sum().item() == 4.0; print('ok')")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=ROOT)
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-500:]
+
+
+def test_stageb_route_table(tmp_path):
+    """csrc/stageb_route.hpp alone decides which stage-B kernel a decode runs. A stand-alone host
+    program prints the route for a table of block sizes; the expected letters are the rule
+    written out by hand: Snip without a full residual or below 16 bytes per sub-block, Small up
+    to 16 word columns (rounded up to whole 4-column chunks), else Regs up to emax = 8 and V2
+    above."""
+    src = tmp_path / "routes.cpp"
+    src.write_text(r'''
+#include "stageb_route.hpp"
+#include <cstdio>
+int main() {
+    const int blocks[] = {64, 128, 136, 264, 512, 520, 1400}, emax[] = {1, 8, 9, 16, 17, 128};
+    for (int B : blocks)
+        for (int full = 0; full < 2; ++full) {
+            const sh::Geometry geo = sh::fixed_geometry(B);
+            std::printf("%d nq=%d full=%d ", B, geo.nq, full);
+            for (int e : emax) {
+                switch (sh::stageb_route(geo, e, full != 0)) {
+                case sh::StageBRoute::Snip: std::putchar('S'); break;
+                case sh::StageBRoute::Regs: std::putchar('R'); break;
+                case sh::StageBRoute::Small: std::putchar('s'); break;
+                case sh::StageBRoute::V2: std::putchar('V'); break;
+                }
+            }
+            std::putchar('\n');
+        }
+    return 0;
+}
+''')
+    exe = tmp_path / "routes"
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-std=c++17", "-Wall", "-Werror", f"-I{os.path.join(ROOT, 'shorthair_amd', 'csrc')}",
+                    str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True, timeout=60).stdout
+    # emax:                           1 8 9 16 17 128
+    assert out.splitlines() == ["64 nq=4 full=0 SSSSSS", "64 nq=4 full=1 SSSSSS",      # sub = 8
+                                "128 nq=4 full=0 SSSSSS", "128 nq=4 full=1 ssssss",
+                                "136 nq=8 full=0 SSSSSS", "136 nq=8 full=1 ssssss",    # nq 5 -> 8
+                                "264 nq=12 full=0 SSSSSS", "264 nq=12 full=1 ssssss",  # nq 9 -> 12
+                                "512 nq=16 full=0 SSSSSS", "512 nq=16 full=1 ssssss",
+                                "520 nq=20 full=0 SSSSSS", "520 nq=20 full=1 RRVVVV",  # nq 17 -> 20
+                                "1400 nq=44 full=0 SSSSSS", "1400 nq=44 full=1 RRVVVV"]

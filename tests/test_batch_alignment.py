@@ -364,9 +364,9 @@ def test_encode_batch_unaligned(sh, shape, mis):
 
 
 DEC_SHAPES = [
-    (28, 4, 256, 37, "fixed"),     # stageb_small2
-    (40, 16, 264, 21, "fixed"),    # stageb_small2
-    (60, 16, 136, 19, "fixed"),    # stageb_small2
+    (28, 4, 256, 37, "fixed"),     # stageb_small
+    (40, 16, 264, 21, "fixed"),    # stageb_small
+    (60, 16, 136, 19, "fixed"),    # stageb_small
     (64, 16, 1400, 7, "fixed"),    # stageb_v2
     (200, 32, 1400, 5, "fixed"),   # stageb_v2
     (190, 66, 1336, 4, "fixed"),   # stageb_v2

@@ -162,3 +162,24 @@ def test_retired_kernel_forms_are_gone(tmp_path, monkeypatch):
         lines = [ln for ln in (tmp_path / f"fixed_k28_m4_{unit}.hip").read_text().splitlines()
                  if ln.startswith("FIXED_KERNEL")]
         assert len(lines) == 1 and re.fullmatch(pat, lines[0]), (unit, lines)
+
+
+def test_retired_stageb_forms_are_gone():
+    """Decode stage B's rejected forms (the LDS-ring stageb_fixed, the one-column stageb_small,
+    the switches that selected them and the three per-kernel argument blocks) are
+    out of the product sources and the tools: stageb.hip holds one kernel per route plus the
+    probe that reports the snippet table's address."""
+    import re
+    csrc = os.path.join(ROOT, "shorthair_amd", "csrc")
+    tools = os.path.join(ROOT, "tools")
+    sources = [os.path.join(d, f) for d in (csrc, tools) for f in sorted(os.listdir(d))
+               if os.path.isfile(os.path.join(d, f))]
+    assert len(sources) > 40
+    for path in sources:
+        text = open(path, errors="replace").read()
+        for s in ("SH_STAGEB_OLD", "SH_V2_MIN", "SH_V2_MAX", "SH_SMALL2", "stageb_small2", "RB_ROW",
+                  "StageBFixedArgs", "StageBV2Args", "StageBSmallArgs"):
+            assert s not in text, (s, path)
+    text = open(os.path.join(csrc, "stageb.hip")).read()
+    kernels = re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", text)
+    assert sorted(kernels) == ["stageb_regs", "stageb_small", "stageb_snip", "stageb_snip_probe", "stageb_v2"]

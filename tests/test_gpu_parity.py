@@ -263,7 +263,7 @@ def _decode_inputs(k, m, B, G, cfg, e_fixed):
                                              # elements per lane at e = 6)
                                              (20, 6, 1400, 999, 6), (12, 5, 64, 300, 5),
                                              (40, 6, 256, 513, 0),
-                                             # small blocks on the compile-time path (stageb_small,
+                                             # small blocks on the compile-time path (route Small: stageb_small,
                                              # nq = 4 / 8 / 12 / 16 word columns, shifted chunks)
                                              (28, 4, 128, 3001, 0), (224, 32, 256, 601, 0),
                                              (112, 16, 384, 333, 16), (200, 32, 136, 257, 0),

@@ -711,7 +711,7 @@ def gen_snippets():
             v = gmul(v, 2)
         lines.append('    "s_setpc_b64 s[40:41]\\n"')
     lines.append('    "sh_snip_end" #SFX ":\\n" ::: "memory")')
-    # Accumulating variant for VGPR-index mode (csrc/stageb.hip, stageb_fixed): snippet c does
+    # Accumulating variant for VGPR-index mode (csrc/stageb.hip, stageb_regs and stageb_v2): snippet c does
     # acc[b] ^= T0[lo(c*2^b)] ^ T1[hi(c*2^b)] as 8 v_bitop3_b32 whose destination and first
     # source are relative to M0 (s_set_gpr_idx_on ..., gpr_idx(SRC0,DST)): the caller selects the
     # output row with s_set_gpr_idx_idx, no copy-and-XOR of a temporary. Every snippet is exactly

@@ -13,5 +13,5 @@ for ctrs in "$@"; do
     python3 tools/run_ops.py --op both --iters 3 > $O/p$i.log 2>&1 || { echo "pass $i ($ctrs) failed"; tail -3 $O/p$i.log; exit 1; }
   python3 tools/pmc_summary.py $O/p$i > $O/pass$i.txt
   rm -rf $O/p$i
-  echo "== pass $i: $ctrs"; grep -A12 "kern_k200_m32_enc\|stageb_fixed" $O/pass$i.txt | grep -v "^--"
+  echo "== pass $i: $ctrs"; grep -A12 "kern_k200_m32_enc\|stageb_v2" $O/pass$i.txt | grep -v "^--"
 done

@@ -3,7 +3,7 @@
 // Each wave runs ROWS input rows; per row it builds the two window tables (22 XORs) and applies
 // 8 coefficients to 8 accumulator sets, in one of these forms:
 //   call   s_swappc into the accumulating snippet of the coefficient (VGPR-index mode), as
-//          stageb_fixed does (2 redirects per product)
+//          stageb_regs and stageb_v2 do (2 redirects per product)
 //   inline the same 8 bitop3 per product inline for a fixed coefficient (no redirect): the floor
 //   call4  as call, 4 outputs per wave (accumulators v[32:63], tables v[64:95]: 5 waves/SIMD,
 //          twice the table builds per product); run with twice the workgroups for equal work

@@ -30,12 +30,11 @@
 #include "frame.hpp"
 #include "kernels.hpp"
 #include "measure.hpp"
+#include "stagea_route.hpp"
 #include "unframe.hpp"
 #include "wire.hpp"
 
 namespace {
-
-using sh::Geometry;
 
 #define SH_CHECK(expr)                                                                        \
     do {                                                                                      \
@@ -283,20 +282,15 @@ uint8_t *generator(Context &c, int k, int m) {
 }
 
 // Whether (k, m, B) can run on the runtime-coefficient tile kernels: fixed_geometry's 16-byte
-// chunks (B/8 >= 16) and a snippet table inside one 4 GB page (the kernels form the snippet
-// addresses from their low dwords).
-bool tile_usable(Context &c, int k, int m, int B) {
+// chunks (B/8 >= 16; tile_shape_ok, the half a host without a GPU answers) and a snippet table
+// inside one 4 GB page (the kernels form the snippet addresses from their low dwords).
+bool tile_shape_ok(int k, int m, int B) {
     if (k < 2 || m < 2 || k + m > 256 || !sh::tile_ok(B)) return false;
-    if (SH_MEASURE_ENV("SH_NO_TILE")) return false;  // measurement switch: the older generic kernels
-    const uint64_t lo = c.snip_base, hi = c.snip_base + static_cast<uint64_t>(sh::SNIP_NULL + 1) * sh::SNIP_STRIDE;
-    return (lo >> 32) == (hi >> 32);
+    return !SH_MEASURE_ENV("SH_NO_TILE");  // measurement switch: the older generic kernels
 }
-
-// Measurement switch (never the default): SH_FORCE_TILE=1 routes shapes that have compile-time
-// kernels through the tile kernels too, to compare the two on the same shape.
-bool force_tile() {
-    static const bool f = SH_MEASURE_ENV("SH_FORCE_TILE") != nullptr;
-    return f;
+bool tile_usable(Context &c, int k, int m, int B) {
+    const uint64_t lo = c.snip_base, hi = c.snip_base + static_cast<uint64_t>(sh::SNIP_NULL + 1) * sh::SNIP_STRIDE;
+    return tile_shape_ok(k, m, B) && (lo >> 32) == (hi >> 32);
 }
 
 // Launch plan of the tile kernels for (k, m): <= 128 rows per launch; per launch and part-wave a
@@ -392,28 +386,98 @@ struct VarSpec {
     int total = 0;
 };
 
-// One launch of a compile-time-scheduled kernel over the whole batch (the kernels build their
-// buffer descriptors per workgroup, so 32-bit offsets never limit the batch size).
-hipError_t launch_fixed_batch(int k, int m, int B, int groups, const uint8_t *in, long long in_gs,
-                              uint8_t *out, long long out_gs, const uint8_t *pos,
-                              const uint8_t *rpos, bool dec, hipStream_t s, const VarSpec *var = nullptr) {
+// What only the single-group ABI (cauchy_256_encode / cauchy_256_decode) asks of the batched
+// paths, which get nullptr from the batch ABI. The last four are decode's.
+struct SingleGroupOpts {
+    // kSliceCap * m * B device bytes that let one group's steps (and stage B's input rows) run as
+    // parallel slices (latency); nullptr = the throughput kernels
+    uint8_t *slice_scratch = nullptr;
+    // pinned host buffer that receives group 0's e_dense recovered rows densely, instead of the
+    // device scatter (the caller knows the recovery positions and places them itself)
+    uint8_t *h_dense = nullptr;
+    int e_dense = 0;
+    uint8_t *ws_ext = nullptr;  // the workspace, carved by the caller in its staging buffer (no lease)
+    bool host_setup = false;    // ... whose setup fields the host wrote (host_decode_setup): no setup kernel
+    // pinned host int that receives group 0's e, copied on the stream while the workspace is still
+    // leased to the call (the caller reads it after synchronising)
+    int *e_host = nullptr;
+};
+
+// Workspace carve for decode of `groups` groups.
+struct DecodeWS {
+    sh::StageAPlan stage_a;  // stage-A kernels (stagea_route.hpp); .kp: position-table stride (a
+                             // compiled K > k codes k, sh::fixed_kernel_k; entries past k stay 0xFF)
+    bool full_residual;     // stage A (compile-time or tile kernels) leaves all m residual rows, and
+                            // the setup writes position tables instead of stage-A coefficients
+    sh::StageBRoute route;  // stage-B kernel (stageb_route.hpp); Snip iff !full_residual
+    int emax, ldA, ldB, nres;  // nres: residual rows per group (m when full_residual, else emax)
+    int *e;
+    uint8_t *rec_idx, *erasures, *coefA, *coefB, *residual, *recovered, *pos, *rpos, *rrow;
+    uint64_t *targets;
+    long long coefA_gs, coefB_gs;
+};
+
+// One pass of encode or of decode stage A over the batch, in the terms every route understands.
+struct StageAJob {
+    int k, m, B, groups;  // var: k = kmax
+    const uint8_t *in;
+    long long in_gs;  // 0 with var: the input is the packed block array
+    uint8_t *out;
+    int n_out;        // output rows per group: m, or emax after a Generic decode stage A
+    const DecodeWS *w;   // decode: its position tables (Fixed, Tile) or per-group coefficients (Generic)
+    const uint8_t *gen;  // Generic encode: the generator's rows [m][round4(k)], shared by the groups
+    const VarSpec *var;
+    uint8_t *slice_scratch;  // StageAPlan::sliced: room for the slices' partial outputs
+};
+
+// Argument block of the compile-time and the tile kernels (they build their buffer descriptors per
+// workgroup, so 32-bit offsets never limit the batch size).
+sh::FixedArgs fixed_args(const StageAJob &j) {
+    const long long out_gs = static_cast<long long>(j.n_out) * j.B;
     sh::FixedArgs a{};
-    a.in = in;
-    a.in_gstride = in_gs;
-    a.in_bytes = static_cast<long long>(groups) * in_gs;
-    a.out = out;
+    a.in = j.in;
+    a.in_gstride = j.in_gs;
+    a.in_bytes = static_cast<long long>(j.groups) * j.in_gs;
+    a.out = j.out;
     a.out_gstride = out_gs;
-    a.out_bytes = static_cast<long long>(groups) * out_gs;
-    a.groups = groups;
-    a.geo = sh::fixed_geometry(B);
-    a.pos = pos;
-    a.rpos = rpos;
-    if (var) {  // k = kmax; the input is the packed block array
-        a.first = var->first;
-        a.total_blocks = var->total;
-        a.in_bytes = static_cast<long long>(var->total) * B;
+    a.out_bytes = static_cast<long long>(j.groups) * out_gs;
+    a.groups = j.groups;
+    a.geo = sh::fixed_geometry(j.B);
+    a.pos = j.w ? j.w->pos : nullptr;
+    a.rpos = j.w ? j.w->rpos : nullptr;
+    if (j.var) {
+        a.first = j.var->first;
+        a.total_blocks = j.var->total;
+        a.in_bytes = static_cast<long long>(j.var->total) * j.B;
     }
-    return sh::launch_fixed(k, m, a, dec, s);
+    return a;
+}
+
+// Argument block of apply_generic: encode shares the generator's rows between the groups (row 0 =
+// coefficient 1 everywhere: M(1) is the identity, i.e. plain XOR; column x of the (kmax, m)
+// generator is column x of every (k <= kmax, m)), decode has per-group rows and row counts.
+sh::ApplyArgs apply_args(Context &c, const StageAJob &j) {
+    sh::ApplyArgs a{};
+    a.in = j.in;
+    a.in_gstride = j.in_gs;
+    a.in_bstride = j.B;
+    a.n_in = j.k;
+    a.out = j.out;
+    a.out_gstride = static_cast<long long>(j.n_out) * j.B;
+    a.out_bstride = j.B;
+    a.n_out = j.n_out;
+    a.n_out_g = j.w ? j.w->e : nullptr;
+    a.coef = j.w ? j.w->coefA : j.gen;
+    a.coef_gstride = j.w ? j.w->coefA_gs : 0;
+    a.coef_ld = j.w ? j.w->ldA : round4(j.k);
+    a.rowbytes = c.d_rowbytes;
+    a.groups = j.groups;
+    a.geo = sh::make_geometry(j.B);
+    if (j.var) {
+        a.first = j.var->first;
+        a.total_blocks = j.var->total;
+    }
+    return a;
 }
 
 // Step slices of the single-group latency path: the k (+ m) serial ring steps of one group are
@@ -429,40 +493,38 @@ int latency_slices(int nsteps) {
     return std::max(1, std::min(std::min(mx, kSliceCap), nsteps / std::max(st, 1)));
 }
 
+// The stage-A plan of (k, m, B) (stagea_route.hpp): the one place the route's inputs are gathered.
+// tile: tile_usable(). latency: the call has slice scratch and one group (SingleGroupOpts).
+// SH_FORCE_TILE=1 (measurement switch) hides the compile-time kernels, to compare the tile kernels.
+sh::StageAPlan stage_a_plan(int k, int m, int B, bool tile, bool dec, bool latency) {
+    static const bool force_tile = SH_MEASURE_ENV("SH_FORCE_TILE") != nullptr;
+    const int slices = latency ? latency_slices(dec ? k + m : k) : 1;
+    return sh::stagea_route(k, force_tile ? 0 : sh::fixed_kernel_k(k, m, B), tile, dec, slices);
+}
+
 // One pass of the tile kernels over the batch (encode, or decode stage A with position tables).
-// slice_scratch (groups == 1 only): room for latency_slices() partial outputs of m * B bytes;
-// the steps are then sliced and the partials XOR-reduced into `out`.
-int launch_tile_batch(Context &c, int k, int m, int B, int groups, const uint8_t *in, long long in_gs,
-                      uint8_t *out, long long out_gs, const uint8_t *pos, const uint8_t *rpos, bool dec,
-                      hipStream_t s, uint8_t *slice_scratch = nullptr, const VarSpec *var = nullptr) {
-    const std::vector<TileLaunch> *plan = tile_plan(c, k, m, dec);
+// sliced (one group): the steps run as latency_slices() slices whose partial outputs of m * B
+// bytes, in j.slice_scratch, are XOR-reduced into j.out.
+int launch_tile_batch(Context &c, const StageAJob &j, bool sliced, hipStream_t s) {
+    const bool dec = j.w != nullptr;
+    const std::vector<TileLaunch> *plan = tile_plan(c, j.k, j.m, dec);
     if (!plan) return -2;
+    const sh::FixedArgs f = fixed_args(j);
     for (const TileLaunch &L : *plan) {
         const int parts = sh::tile_parts(L.nrows);
         const int S = sh::tile_steps_per_group(parts);
-        const int ns = (slice_scratch && groups == 1) ? latency_slices(L.nsteps) : 1;
+        const int ns = sliced ? latency_slices(L.nsteps) : 1;
+        const long long row0_bytes = static_cast<long long>(L.row0) * j.B;
         sh::TileArgs t{};
-        t.f.in = in;
-        t.f.in_gstride = in_gs;
-        t.f.in_bytes = static_cast<long long>(groups) * in_gs;
-        t.f.out = out + static_cast<long long>(L.row0) * B;
-        t.f.out_gstride = out_gs;
-        t.f.out_bytes = static_cast<long long>(groups) * out_gs - static_cast<long long>(L.row0) * B;
-        t.f.groups = groups;
-        t.f.geo = sh::fixed_geometry(B);
-        t.f.pos = pos;
-        t.f.rpos = rpos;
-        if (var) {  // k = kmax; the input is the packed block array
-            t.f.first = var->first;
-            t.f.total_blocks = var->total;
-            t.f.in_bytes = static_cast<long long>(var->total) * B;
-        }
+        t.f = f;
+        t.f.out = j.out + row0_bytes;
+        t.f.out_bytes = f.out_bytes - row0_bytes;
         t.targets = L.targets;
         t.tstride = L.tstride;
         t.snip_hi = L.hi;
         t.col = L.col ? 1 : 0;
-        t.k = k;
-        t.m = m;
+        t.k = j.k;
+        t.m = j.m;
         t.row0 = L.row0;
         t.nrows = L.nrows;
         t.nsteps = L.nsteps;
@@ -472,145 +534,88 @@ int launch_tile_batch(Context &c, int k, int m, int B, int groups, const uint8_t
             const int per = ((L.nsteps + ns - 1) / ns + S - 1) / S * S;
             t.slice_steps = per;
             t.slices = (L.nsteps + per - 1) / per;
-            t.out_slice_bytes = out_gs;
-            t.f.out = slice_scratch + static_cast<long long>(L.row0) * B;
-            t.f.out_bytes = out_gs - static_cast<long long>(L.row0) * B;
-            SH_CHECK(sh::launch_tile(t, dec, s));
-            SH_CHECK(sh::launch_xor_reduce(slice_scratch + static_cast<long long>(L.row0) * B, out_gs, t.slices,
-                                           out + static_cast<long long>(L.row0) * B,
-                                           static_cast<long long>(L.nrows) * B, s));
-        } else {
-            SH_CHECK(sh::launch_tile(t, dec, s));
+            t.out_slice_bytes = f.out_gstride;
+            t.f.out = j.slice_scratch + row0_bytes;
+            t.f.out_bytes = f.out_gstride - row0_bytes;
         }
+        SH_CHECK(sh::launch_tile(t, dec, s));
+        if (ns > 1)
+            SH_CHECK(sh::launch_xor_reduce(j.slice_scratch + row0_bytes, f.out_gstride, t.slices, j.out + row0_bytes,
+                                           static_cast<long long>(L.nrows) * j.B, s));
     }
     return 0;
+}
+
+// Encode or decode stage A by the route of its plan.
+int launch_stage_a(Context &c, const sh::StageAPlan &plan, const StageAJob &j, hipStream_t s) {
+    switch (plan.route) {
+    case sh::StageARoute::Fixed:
+        SH_CHECK(sh::launch_fixed(j.k, j.m, fixed_args(j), j.w != nullptr, s));
+        return 0;
+    case sh::StageARoute::Tile:
+        return launch_tile_batch(c, j, plan.sliced, s);
+    default:  // Generic; decode: per-group rows
+        SH_CHECK(sh::launch_apply(apply_args(c, j), j.w != nullptr, s));
+        return 0;
+    }
 }
 
 // ---- batched encode ----
-// slice_scratch (single-group ABI): kSliceCap * m * B device bytes that let one group's steps run as
-// parallel slices on the tile kernels (latency); nullptr = the throughput kernels.
-int encode_batch(int k, int m, int B, int groups, const uint8_t *d_in, uint8_t *d_out,
-                 hipStream_t s, uint8_t *slice_scratch = nullptr) {
+// var (cauchy_256_encode_batch_var; parameters already checked, k = kmax): the same kernels in
+// their var-k form, one launch for every k_g <= kmax, after a small launch that counts the
+// malformed groups into the stream's error counter.
+int encode_batch(int k, int m, int B, int groups, const VarSpec *var, const uint8_t *d_in, uint8_t *d_out,
+                 hipStream_t s, const SingleGroupOpts *sg) {
     Context &c = ctx();
     DeviceScope ds(c);
     if (ds.rc) return ds.rc;
-    if (groups <= 0 || m <= 0 || k <= 0 || B <= 0) return 0;
-    const long long in_gs = static_cast<long long>(k) * B, out_gs = static_cast<long long>(m) * B;
-    if (k <= 1) {  // reference cauchy_256.cpp:1485-1493
-        SH_CHECK(sh::launch_copy_first(d_in, in_gs, d_out, out_gs, m, B, groups, s));
-        return 0;
+    const long long in_gs = var ? 0 : static_cast<long long>(k) * B, out_gs = static_cast<long long>(m) * B;
+    if (groups <= 0 || m <= 0 || k <= 0 || B <= 0) return 0;  // (var: only groups can be 0)
+    if (var) {
+        StreamState *st = stream_state(c, s);
+        if (!st) return -2;
+        {
+            // under the stream's lock, like a decode's count: cauchy_256_batch_errors reads and
+            // clears the counter either before this call's count or after it
+            std::lock_guard<std::mutex> g(st->mu);
+            SH_CHECK(sh::launch_var_check(var->first, var->total, k, groups, st->d_errors, s));
+        }
+        if (m == 1) {
+            SH_CHECK(sh::launch_xor_rows_var(d_in, var->first, var->total, k, d_out, out_gs, B, groups, s));
+            return 0;
+        }
+    } else {
+        if (k <= 1) {  // reference cauchy_256.cpp:1485-1493
+            SH_CHECK(sh::launch_copy_first(d_in, in_gs, d_out, out_gs, m, B, groups, s));
+            return 0;
+        }
+        const bool valid = (k + m <= 256) && (B % 8 == 0);
+        if (m == 1 || !valid) {
+            // Row 0 (plain XOR, any B) is written even when the parameters are then rejected
+            // (reference cauchy_256.cpp:1496-1511).
+            SH_CHECK(sh::launch_xor_rows(d_in, in_gs, k, d_out, out_gs, B, groups, s));
+            return (m == 1 || valid) ? 0 : -1;  // m == 1 returns before validation (:1503-1506)
+        }
     }
-    const bool valid = (k + m <= 256) && (B % 8 == 0);
-    if (m == 1 || !valid) {
-        // Row 0 (plain XOR, any B) is written even when the parameters are then rejected
-        // (reference cauchy_256.cpp:1496-1511).
-        SH_CHECK(sh::launch_xor_rows(d_in, in_gs, k, d_out, out_gs, B, groups, s));
-        return (m == 1 || valid) ? 0 : -1;  // m == 1 returns before validation (:1503-1506)
-    }
-    const bool sliced = slice_scratch && groups == 1 && tile_usable(c, k, m, B) && latency_slices(k) > 1;
-    if (sh::has_fixed(k, m, B) && !force_tile() && !sliced) {
-        SH_CHECK(launch_fixed_batch(k, m, B, groups, d_in, in_gs, d_out, out_gs, nullptr, nullptr, false, s));
-        return 0;
-    }
-    if (tile_usable(c, k, m, B))
-        return launch_tile_batch(c, k, m, B, groups, d_in, in_gs, d_out, out_gs, nullptr, nullptr, false, s,
-                                 sliced ? slice_scratch : nullptr);
-    uint8_t *gen = generator(c, k, m);
-    if (!gen) return -2;
-    sh::ApplyArgs a{};
-    a.in = d_in;
-    a.in_gstride = in_gs;
-    a.in_bstride = B;
-    a.n_in = k;
-    a.out = d_out;
-    a.out_gstride = out_gs;
-    a.out_bstride = B;
-    a.n_out = m;  // row 0 = coefficient 1 everywhere: M(1) is the identity, i.e. plain XOR
-    a.n_out_g = nullptr;
-    a.coef = gen;
-    a.coef_gstride = 0;
-    a.coef_ld = round4(k);
-    a.rowbytes = c.d_rowbytes;
-    a.groups = groups;
-    a.geo = sh::make_geometry(B);
-    SH_CHECK(sh::launch_apply(a, false, s));
-    return 0;
+    StageAJob j{k, m, B, groups, d_in, in_gs, d_out, /*n_out=*/m};
+    j.var = var;
+    j.slice_scratch = sg ? sg->slice_scratch : nullptr;
+    const bool latency = j.slice_scratch && groups == 1;
+    const sh::StageAPlan plan = stage_a_plan(k, m, B, tile_usable(c, k, m, B), /*dec=*/false, latency);
+    if (plan.route == sh::StageARoute::Generic && !(j.gen = generator(c, k, m))) return -2;
+    return launch_stage_a(c, plan, j, s);
 }
 
-// Var-k encode (cauchy_256_encode_batch_var; parameters already checked): the kernels of
-// cauchy_256_batch_path(kmax, m, B) in their var-k form, one launch for every k_g <= kmax, and a
-// small launch that counts the malformed groups into the stream's error counter.
-int encode_batch_var(int kmax, int m, int B, int groups, const VarSpec &var, const uint8_t *d_in, uint8_t *d_out,
-                     hipStream_t s) {
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    if (groups <= 0) return 0;
-    StreamState *st = stream_state(c, s);
-    if (!st) return -2;
-    const long long out_gs = static_cast<long long>(m) * B;
-    {
-        // under the stream's lock, like a decode's count: cauchy_256_batch_errors reads and clears
-        // the counter either before this call's count or after it
-        std::lock_guard<std::mutex> g(st->mu);
-        SH_CHECK(sh::launch_var_check(var.first, var.total, kmax, groups, st->d_errors, s));
-    }
-    if (m == 1) {
-        SH_CHECK(sh::launch_xor_rows_var(d_in, var.first, var.total, kmax, d_out, out_gs, B, groups, s));
-        return 0;
-    }
-    if (sh::has_fixed(kmax, m, B) && !force_tile()) {
-        SH_CHECK(launch_fixed_batch(kmax, m, B, groups, d_in, 0, d_out, out_gs, nullptr, nullptr, false, s, &var));
-        return 0;
-    }
-    if (tile_usable(c, kmax, m, B))
-        return launch_tile_batch(c, kmax, m, B, groups, d_in, 0, d_out, out_gs, nullptr, nullptr, false, s, nullptr,
-                                 &var);
-    uint8_t *gen = generator(c, kmax, m);
-    if (!gen) return -2;
-    sh::ApplyArgs a{};
-    a.in = d_in;
-    a.in_bstride = B;
-    a.n_in = kmax;
-    a.out = d_out;
-    a.out_gstride = out_gs;
-    a.out_bstride = B;
-    a.n_out = m;
-    a.coef = gen;  // column x of the (kmax, m) generator is column x of every (k <= kmax, m)
-    a.coef_ld = round4(kmax);
-    a.rowbytes = c.d_rowbytes;
-    a.groups = groups;
-    a.geo = sh::make_geometry(B);
-    a.first = var.first;
-    a.total_blocks = var.total;
-    SH_CHECK(sh::launch_apply(a, false, s));
-    return 0;
-}
-
-// Workspace carve for decode of `groups` groups.
-struct DecodeWS {
-    bool full_residual;     // stage A (compile-time or tile kernels) leaves all m residual rows, and
-                            // the setup writes position tables instead of stage-A coefficients
-    sh::StageBRoute route;  // stage-B kernel (stageb_route.hpp); Snip iff !full_residual
-    int emax, ldA, ldB, nres;  // nres: residual rows per group (m when full_residual, else emax)
-    int kp;           // position-table stride: round4 of the stage-A kernel's K (a compiled K > k
-                      // codes k, sh::fixed_kernel_k; the entries past k stay 0xFF)
-    int *e;
-    uint8_t *rec_idx, *erasures, *coefA, *coefB, *residual, *recovered, *pos, *rpos, *rrow;
-    uint64_t *targets;
-    long long coefA_gs, coefB_gs;
-};
-
-size_t carve(DecodeWS &w, uint8_t *base, int k, int m, int B, int groups, bool need_recovered) {
+// latency: the decode has slice scratch and one group (stage_a_plan; the layout does not depend on it).
+size_t carve(DecodeWS &w, uint8_t *base, int k, int m, int B, int groups, bool need_recovered, bool latency) {
     const sh::Geometry geo = sh::fixed_geometry(B);
     w.emax = std::min(k, m);
+    w.stage_a = stage_a_plan(k, m, B, tile_usable(ctx(), k, m, B), /*dec=*/true, latency);
     // stage A over all m rows (compile-time or tile kernels) and position tables, where the
     // geometry lets a residual stage-B kernel follow
-    w.route = sh::stageb_route(geo, w.emax, sh::has_fixed(k, m, B) || tile_usable(ctx(), k, m, B));
+    w.route = sh::stageb_route(geo, w.emax, w.stage_a.route != sh::StageARoute::Generic);
     w.full_residual = w.route != sh::StageBRoute::Snip;
     const bool regs = w.route == sh::StageBRoute::Regs;
-    const int kfix = force_tile() ? 0 : sh::fixed_kernel_k(k, m, B);
-    w.kp = round4(std::max(k, kfix));
     w.ldA = w.full_residual ? 0 : round4(k);
     w.ldB = (w.emax + 7) & ~7;  // stage-B coefficients [i][ldB] (transposed, 8-entry rows)
     w.nres = w.full_residual ? m : w.emax;
@@ -631,7 +636,7 @@ size_t carve(DecodeWS &w, uint8_t *base, int k, int m, int B, int groups, bool n
     w.coefB = regs ? nullptr : take(G * w.coefB_gs);
     w.targets = regs ? reinterpret_cast<uint64_t *>(take(G * w.emax * w.ldB * sizeof(uint64_t))) : nullptr;
     w.rrow = w.full_residual ? take(G * round4(w.emax)) : nullptr;
-    w.pos = w.full_residual ? take(G * w.kp) : nullptr;
+    w.pos = w.full_residual ? take(G * w.stage_a.kp) : nullptr;
     w.rpos = w.full_residual ? take(G * round4(m)) : nullptr;
     w.residual = take(G * w.nres * static_cast<size_t>(B) + 256);  // + slack: word over-read
     w.recovered = need_recovered ? take(G * w.emax * static_cast<size_t>(B)) : nullptr;
@@ -705,11 +710,10 @@ hipError_t launch_stage_b(const DecodeWS &w, int n_in, int B, int groups, uint8_
 
 // Common decode core (m >= 2, valid params): writes recovered blocks densely into `dst`
 // ([G][emax][B]) and leaves per-group e / rec_idx / erasures in the workspace.
-// host_setup: the workspace's setup fields were written by the host (single-group ABI,
-// host_decode_setup below) and arrive with the blocks: no setup kernel.
 int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_blocks,
                 const uint8_t *d_rows, DecodeWS &w, int *errors, uint8_t *dst, hipStream_t s,
-                uint8_t *slice_scratch = nullptr, bool host_setup = false, const VarSpec *var = nullptr) {
+                const VarSpec *var, const SingleGroupOpts *sg) {
+    uint8_t *slice_scratch = sg ? sg->slice_scratch : nullptr;
     uint8_t *gen = generator(c, k, m);
     if (!gen) return -2;
     sh::DecodeSetupArgs sa{};
@@ -733,7 +737,7 @@ int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_bl
     sa.coefB_gstride = w.coefB_gs;
     sa.ldB = w.ldB;
     sa.pos = w.pos;
-    sa.kp = w.kp;
+    sa.kp = w.stage_a.kp;
     sa.rpos = w.rpos;
     sa.rrow = w.rrow;
     sa.ldR = round4(w.emax);
@@ -760,54 +764,22 @@ int decode_core(Context &c, int k, int m, int B, int groups, const uint8_t *d_bl
         ev_all = !c.ev_stage_a_only;
     }
     if (ev && ev_all) SH_CHECK(hipEventRecord(ev[0], s));
-    if (!host_setup) SH_CHECK(sh::launch_decode_setup(sa, groups, s));
+    if (!(sg && sg->host_setup)) SH_CHECK(sh::launch_decode_setup(sa, groups, s));
     if (ev) SH_CHECK(hipEventRecord(ev[1], s));
 
-    const Geometry geo = sh::make_geometry(B);
-    if (w.full_residual) {
-        // Stage A (compile-time generator, all m rows, erased columns read as zeros):
-        //   residual_y = R_y + sum_{received x} M(C[y][x]) d_x
-        // (the tile kernels read position tables round4(k) wide: not after a wider compiled K)
-        const bool sliced = slice_scratch && groups == 1 && tile_usable(c, k, m, B) && latency_slices(k + m) > 1 &&
-                            w.kp == round4(k);
-        if (sh::has_fixed(k, m, B) && !force_tile() && !sliced) {
-            SH_CHECK(launch_fixed_batch(k, m, B, groups, d_blocks, static_cast<long long>(k) * B,
-                                        w.residual, static_cast<long long>(m) * B, w.pos, w.rpos, true, s, var));
-        } else if (int rc = launch_tile_batch(c, k, m, B, groups, d_blocks, static_cast<long long>(k) * B,
-                                              w.residual, static_cast<long long>(m) * B, w.pos, w.rpos, true, s,
-                                              sliced ? slice_scratch : nullptr, var)) {
-            return rc;
-        }
-        if (ev) SH_CHECK(hipEventRecord(ev[2], s));
-        // Stage B: recovered_j = sum_y M(S^-1[j][i(y)]) residual_y over the received rows y
-        SH_CHECK(launch_stage_b(w, m, B, groups, dst, s, groups == 1 ? slice_scratch : nullptr));
-        if (ev && ev_all) SH_CHECK(hipEventRecord(ev[3], s));
-        return 0;
-    }
-    // Stage A: residual_i = R_i + sum_{orig j} M(C[r_i][row_j]) d_j  (per-group coefficients)
-    sh::ApplyArgs a{};
-    a.in = d_blocks;
-    a.in_gstride = static_cast<long long>(k) * B;
-    a.in_bstride = B;
-    a.n_in = k;
-    a.out = w.residual;
-    a.out_gstride = static_cast<long long>(w.emax) * B;
-    a.out_bstride = B;
-    a.n_out = w.emax;
-    a.n_out_g = w.e;
-    a.coef = w.coefA;
-    a.coef_gstride = w.coefA_gs;
-    a.coef_ld = w.ldA;
-    a.rowbytes = c.d_rowbytes;
-    a.groups = groups;
-    a.geo = geo;
-    if (var) {
-        a.first = var->first;
-        a.total_blocks = var->total;
-    }
-    SH_CHECK(sh::launch_apply(a, true, s));
-    // Stage B: recovered_j = sum_i M(S^-1[j][i]) residual_i
-    SH_CHECK(launch_stage_b(w, w.emax, B, groups, dst, s));
+    // Stage A. Fixed, Tile (compile-time generator, all m rows, erased columns read as zeros):
+    //   residual_y = R_y + sum_{received x} M(C[y][x]) d_x
+    // Generic (per-group coefficients, the emax rows of the received recovery blocks):
+    //   residual_i = R_i + sum_{orig j} M(C[r_i][row_j]) d_j
+    StageAJob j{k, m, B, groups, d_blocks, static_cast<long long>(k) * B, w.residual, /*n_out=*/w.nres, &w};
+    j.var = var;
+    j.slice_scratch = slice_scratch;
+    if (int rc = launch_stage_a(c, w.stage_a, j, s)) return rc;
+    // (the events past the setup are recorded after a full-residual stage A only)
+    if (ev && w.full_residual) SH_CHECK(hipEventRecord(ev[2], s));
+    // Stage B: recovered_j = sum_i M(S^-1[j][i]) (residual of the i-th received recovery block)
+    SH_CHECK(launch_stage_b(w, w.nres, B, groups, dst, s, groups == 1 ? slice_scratch : nullptr));
+    if (ev && ev_all && w.full_residual) SH_CHECK(hipEventRecord(ev[3], s));
     return 0;
 }
 
@@ -835,7 +807,7 @@ bool host_decode_setup(const DecodeWS &w, int k, int m, const uint8_t *rows, int
     sh::cauchy_params(k, m, xp, yp);
     *w.e = e;
     std::memset(w.rrow, 0, round4(w.emax));
-    std::memset(w.pos, 0xFF, w.kp);
+    std::memset(w.pos, 0xFF, w.stage_a.kp);
     std::memset(w.rpos, 0xFF, round4(m));
     for (int j = 0; j < k; ++j) {
         if (rows[j] < k) w.pos[rows[j]] = static_cast<uint8_t>(j);
@@ -870,17 +842,8 @@ bool host_decode_setup(const DecodeWS &w, int k, int m, const uint8_t *rows, int
     return true;
 }
 
-// e_host (optional, pinned host memory): receives group 0's e, copied on `s` while the workspace
-// is still leased to this call (the single-group ABI reads it after synchronising).
-// h_dense (single-group ABI, optional): the e_dense recovered rows of group 0 are copied densely
-// into this pinned buffer instead of being scattered on the device (the caller knows the
-// recovery positions and places them itself).
-// ws_ext (single-group ABI, optional): the workspace, carved by the caller in its staging
-// buffer (no lease); host_setup: its setup fields are already there (decode_core).
-int decode_batch(int k, int m, int B, int groups, uint8_t *d_blocks, uint8_t *d_rows,
-                 hipStream_t s, int *e_host = nullptr, uint8_t *slice_scratch = nullptr,
-                 uint8_t *h_dense = nullptr, int e_dense = 0, uint8_t *ws_ext = nullptr,
-                 bool host_setup = false) {
+int decode_batch(int k, int m, int B, int groups, uint8_t *d_blocks, uint8_t *d_rows, hipStream_t s,
+                 const SingleGroupOpts *sg) {
     Context &c = ctx();
     DeviceScope ds(c);
     if (ds.rc) return ds.rc;
@@ -894,20 +857,21 @@ int decode_batch(int k, int m, int B, int groups, uint8_t *d_blocks, uint8_t *d_
         return 0;
     }
     if (k + m > 256 || B % 8 != 0) return invalid_decode_status(k, groups, d_rows, s);
+    const SingleGroupOpts none, &o = sg ? *sg : none;
+    const bool latency = o.slice_scratch && groups == 1;
     DecodeWS w{};
     WsLease ls;
-    if (ws_ext) {
-        carve(w, ws_ext, k, m, B, groups, true);
-    } else {
+    if (!o.ws_ext) {
         // slice_scratch: the single-group ABI (a staging stream, no batch reserve)
-        if (int rc = lease_workspace(c, s, carve(w, nullptr, k, m, B, groups, true), ls, slice_scratch == nullptr)) return rc;
-        carve(w, ls.p, k, m, B, groups, true);
+        const size_t need = carve(w, nullptr, k, m, B, groups, true, latency);
+        if (int rc = lease_workspace(c, s, need, ls, o.slice_scratch == nullptr)) return rc;
     }
-    if (int rc = decode_core(c, k, m, B, groups, d_blocks, d_rows, w, ws_ext ? nullptr : ls.errors, w.recovered, s,
-                             slice_scratch, host_setup))
+    carve(w, o.ws_ext ? o.ws_ext : ls.p, k, m, B, groups, true, latency);
+    if (int rc = decode_core(c, k, m, B, groups, d_blocks, d_rows, w, o.ws_ext ? nullptr : ls.errors, w.recovered, s,
+                             nullptr, sg))
         return rc;
-    if (h_dense) {  // still under the workspace lease: the copy is ordered before any regrowth
-        SH_CHECK(hipMemcpyAsync(h_dense, w.recovered, static_cast<size_t>(e_dense) * B, hipMemcpyDeviceToHost, s));
+    if (o.h_dense) {  // still under the workspace lease: the copy is ordered before any regrowth
+        SH_CHECK(hipMemcpyAsync(o.h_dense, w.recovered, static_cast<size_t>(o.e_dense) * B, hipMemcpyDeviceToHost, s));
         return 0;
     }
     sh::ScatterArgs sc{};
@@ -923,7 +887,7 @@ int decode_batch(int k, int m, int B, int groups, uint8_t *d_blocks, uint8_t *d_
     sc.emax = w.emax;
     sc.B = B;
     SH_CHECK(sh::launch_scatter(sc, groups, s));
-    if (e_host) SH_CHECK(hipMemcpyAsync(e_host, w.e, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (o.e_host) SH_CHECK(hipMemcpyAsync(o.e_host, w.e, sizeof(int), hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -940,19 +904,44 @@ extern "C" int cauchy_256_batch_init(int device) {
 
 extern "C" int cauchy_256_encode_batch(int k, int m, int block_bytes, int groups,
                                        const void *d_data, void *d_recovery, void *stream) {
-    return encode_batch(k, m, block_bytes, groups, static_cast<const uint8_t *>(d_data),
-                        static_cast<uint8_t *>(d_recovery), pick(stream));
+    return encode_batch(k, m, block_bytes, groups, nullptr, static_cast<const uint8_t *>(d_data),
+                        static_cast<uint8_t *>(d_recovery), pick(stream), nullptr);
 }
 
 extern "C" int cauchy_256_decode_batch(int k, int m, int block_bytes, int groups, void *d_blocks,
                                        unsigned char *d_rows, void *stream) {
-    return decode_batch(k, m, block_bytes, groups, static_cast<uint8_t *>(d_blocks), d_rows,
-                        pick(stream));
+    return decode_batch(k, m, block_bytes, groups, static_cast<uint8_t *>(d_blocks), d_rows, pick(stream), nullptr);
 }
 
-extern "C" int cauchy_256_decode_batch_out(int k, int m, int block_bytes, int groups,
-                                           const void *d_blocks, const unsigned char *d_rows,
-                                           void *d_out, unsigned char *d_out_rows,
+namespace {
+// cauchy_256_decode_batch_out(_var) after their parameter checks (k, m >= 2, k + m <= 256,
+// B % 8 == 0, groups > 0). var: k = kmax, and the workspace is the uniform (kmax, m) decode's, so
+// cauchy_256_batch_reserve(kmax, ...) covers it.
+int decode_batch_out(Context &c, int k, int m, int B, int groups, const VarSpec *var, const void *d_blocks,
+                     const unsigned char *d_rows, void *d_out, unsigned char *d_out_rows, int *d_out_count,
+                     hipStream_t s) {
+    DecodeWS w{};
+    WsLease ls;
+    const bool need_recovered = false, latency = false;  // straight into d_out; the throughput kernels
+    if (int rc = lease_workspace(c, s, carve(w, nullptr, k, m, B, groups, need_recovered, latency), ls)) return rc;
+    carve(w, ls.p, k, m, B, groups, need_recovered, latency);
+    // the setup writes the erasure list ([G][emax]) and the counts ([G]) straight into the
+    // caller's outputs (same layouts as the workspace's): no copies after the decode
+    w.erasures = d_out_rows;
+    w.e = d_out_count;
+    return decode_core(c, k, m, B, groups, static_cast<const uint8_t *>(d_blocks), d_rows, w, ls.errors,
+                       static_cast<uint8_t *>(d_out), s, var, nullptr);
+}
+
+// Host-checked parameters of the var-k calls (cauchy_256_batch.h): false = -1, nothing enqueued.
+bool var_params_ok(int kmax, int m, int mmin, int B, int groups, int total_blocks) {
+    return kmax >= 2 && kmax <= 255 && m >= mmin && kmax + m <= 256 && B > 0 && B % 8 == 0 && groups >= 0 &&
+           total_blocks >= 0 && static_cast<long long>(total_blocks) <= static_cast<long long>(groups) * kmax;
+}
+}  // namespace
+
+extern "C" int cauchy_256_decode_batch_out(int k, int m, int block_bytes, int groups, const void *d_blocks,
+                                           const unsigned char *d_rows, void *d_out, unsigned char *d_out_rows,
                                            int *d_out_count, void *stream) {
     Context &c = ctx();
     DeviceScope ds(c);
@@ -961,35 +950,16 @@ extern "C" int cauchy_256_decode_batch_out(int k, int m, int block_bytes, int gr
     if (k < 2 || m < 2) return -1;
     hipStream_t s = pick(stream);
     if (k + m > 256 || block_bytes % 8 != 0) return invalid_decode_status(k, groups, d_rows, s);
-    DecodeWS w{};
-    WsLease ls;
-    if (int rc = lease_workspace(c, s, carve(w, nullptr, k, m, block_bytes, groups, false), ls)) return rc;
-    carve(w, ls.p, k, m, block_bytes, groups, false);
-    // the setup writes the erasure list ([G][emax]) and the counts ([G]) straight into the
-    // caller's outputs (same layouts as the workspace's): no copies after the decode
-    w.erasures = d_out_rows;
-    w.e = d_out_count;
-    return decode_core(c, k, m, block_bytes, groups, static_cast<const uint8_t *>(d_blocks), d_rows, w,
-                       ls.errors, static_cast<uint8_t *>(d_out), s);
+    return decode_batch_out(c, k, m, block_bytes, groups, nullptr, d_blocks, d_rows, d_out, d_out_rows, d_out_count, s);
 }
-
-namespace {
-// Host-checked parameters of the var-k calls (cauchy_256_batch.h): false = -1, nothing enqueued.
-bool var_params_ok(int kmax, int m, int mmin, int B, int groups, int total_blocks) {
-    return kmax >= 2 && kmax <= 255 && m >= mmin && kmax + m <= 256 && B > 0 && B % 8 == 0 && groups >= 0 &&
-           total_blocks >= 0 && static_cast<long long>(total_blocks) <= static_cast<long long>(groups) * kmax;
-}
-}  // namespace
 
 extern "C" int cauchy_256_encode_batch_var(int kmax, int m, int block_bytes, int groups, const int *d_first,
                                            int total_blocks, const void *d_data, void *d_recovery,
                                            void *stream) {
     if (!var_params_ok(kmax, m, 1, block_bytes, groups, total_blocks)) return -1;
-    VarSpec var;
-    var.first = d_first;
-    var.total = total_blocks;
-    return encode_batch_var(kmax, m, block_bytes, groups, var, static_cast<const uint8_t *>(d_data),
-                            static_cast<uint8_t *>(d_recovery), pick(stream));
+    const VarSpec var{d_first, total_blocks};
+    return encode_batch(kmax, m, block_bytes, groups, &var, static_cast<const uint8_t *>(d_data),
+                        static_cast<uint8_t *>(d_recovery), pick(stream), nullptr);
 }
 
 extern "C" int cauchy_256_decode_batch_out_var(int kmax, int m, int block_bytes, int groups, const int *d_first,
@@ -1001,19 +971,9 @@ extern "C" int cauchy_256_decode_batch_out_var(int kmax, int m, int block_bytes,
     DeviceScope ds(c);
     if (ds.rc) return ds.rc;
     if (groups <= 0) return 0;
-    hipStream_t s = pick(stream);
-    VarSpec var;
-    var.first = d_first;
-    var.total = total_blocks;
-    // the workspace of the uniform (kmax, m) decode: cauchy_256_batch_reserve(kmax, ...) covers it
-    DecodeWS w{};
-    WsLease ls;
-    if (int rc = lease_workspace(c, s, carve(w, nullptr, kmax, m, block_bytes, groups, false), ls)) return rc;
-    carve(w, ls.p, kmax, m, block_bytes, groups, false);
-    w.erasures = d_out_rows;
-    w.e = d_out_count;
-    return decode_core(c, kmax, m, block_bytes, groups, static_cast<const uint8_t *>(d_blocks), d_rows, w,
-                       ls.errors, static_cast<uint8_t *>(d_out), s, nullptr, false, &var);
+    const VarSpec var{d_first, total_blocks};
+    return decode_batch_out(c, kmax, m, block_bytes, groups, &var, d_blocks, d_rows, d_out, d_out_rows, d_out_count,
+                            pick(stream));
 }
 
 extern "C" int shorthair_frame_batch(int block_bytes, int total_blocks, const void *d_payload,
@@ -1029,7 +989,7 @@ extern "C" int shorthair_frame_batch(int block_bytes, int total_blocks, const vo
     hipStream_t s = pick(stream);
     StreamState *st = stream_state(c, s);
     if (!st) return -2;
-    // under the stream's lock, like the var-k encode's count (encode_batch_var)
+    // under the stream's lock, like the var-k encode's count (encode_batch)
     std::lock_guard<std::mutex> g(st->mu);
     SH_CHECK(sh::launch_frame(block_bytes, total_blocks, static_cast<const uint8_t *>(d_payload), payload_bytes,
                               d_off, d_len, d_raw, static_cast<uint8_t *>(d_blocks), st->d_errors, s));
@@ -1099,12 +1059,10 @@ extern "C" int cauchy_256_batch_reserve_stream(int k, int m, int block_bytes, in
     if (ds.rc) return ds.rc;
     if (k < 2 || m < 2 || k + m > 256 || block_bytes <= 0 || groups <= 0) return 0;
     DecodeWS w{};
-    const size_t need = carve(w, nullptr, k, m, block_bytes, groups, true);
+    const size_t need = carve(w, nullptr, k, m, block_bytes, groups, /*need_recovered=*/true, /*latency=*/false);
     if (!generator(c, k, m)) return -2;
     // the tile kernels' snippet-address tables of this shape, so a later decode allocates nothing
-    if (block_bytes % 8 == 0 && (!sh::has_fixed(k, m, block_bytes) || force_tile()) &&
-        tile_usable(c, k, m, block_bytes) && !tile_plan(c, k, m, true))
-        return -2;
+    if (w.stage_a.route == sh::StageARoute::Tile && !tile_plan(c, k, m, true)) return -2;
     size_t cur = c.ws_reserve.load();
     while (cur < need && !c.ws_reserve.compare_exchange_weak(cur, need)) {
     }
@@ -1189,15 +1147,15 @@ extern "C" int cauchy_256_erasure_pattern(unsigned long long g, int k, int m, un
 
 extern "C" int cauchy_256_batch_path(int k, int m, int block_bytes) {
     if (k < 1 || m < 1 || k + m > 256 || block_bytes <= 0 || block_bytes % 8 != 0) return -1;
-    if (sh::has_fixed(k, m, block_bytes) && !force_tile()) return 1;
     // Host-only answer (a launcher may ask before it spawns rank processes, so this never
     // initialises the GPU): the snippet table's one-4-GB-page condition needs the loaded code
     // object and is checked at launch (generic kernels otherwise); once the library is
     // initialised the answer includes it.
-    if (k < 2 || m < 2 || !sh::tile_ok(block_bytes) || SH_MEASURE_ENV("SH_NO_TILE")) return 0;
     Context &c = ctx();
     std::lock_guard<std::mutex> g(c.mu);
-    return !c.ready || tile_usable(c, k, m, block_bytes) ? 2 : 0;
+    const bool tile = c.ready ? tile_usable(c, k, m, block_bytes) : tile_shape_ok(k, m, block_bytes);
+    const sh::StageARoute r = stage_a_plan(k, m, block_bytes, tile, /*dec=*/false, /*latency=*/false).route;
+    return r == sh::StageARoute::Fixed ? 1 : r == sh::StageARoute::Tile ? 2 : 0;
 }
 
 extern "C" void *cauchy_256_default_stream(void) {
@@ -1347,7 +1305,9 @@ extern "C" int cauchy_256_encode(int k, int m, const unsigned char *data_ptrs[],
     uint8_t *d = static_cast<uint8_t *>(st.d.p);
     for (int x = 0; x < kin; ++x) std::memcpy(h + static_cast<size_t>(x) * block_bytes, data_ptrs[x], block_bytes);
     SH_CHECK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st.stream));
-    const int rc = encode_batch(k, m, block_bytes, 1, d, d + in_bytes, st.stream, d + in_bytes + out_bytes);
+    SingleGroupOpts sg;
+    sg.slice_scratch = d + in_bytes + out_bytes;
+    const int rc = encode_batch(k, m, block_bytes, 1, nullptr, d, d + in_bytes, st.stream, &sg);
     if (rc == -2) {
         (void)hipStreamSynchronize(st.stream);  // the slot is released on return
         return rc;
@@ -1395,7 +1355,7 @@ extern "C" int cauchy_256_decode(int k, int m, Block *blocks, int block_bytes) {
     // staging: [blocks][rows (256)][workspace (general path)][slice partials]
     const size_t ws_off = (data_bytes + 256 + 255) & ~static_cast<size_t>(255);
     DecodeWS probe{};
-    const size_t ws_bytes = general ? carve(probe, nullptr, k, m, block_bytes, 1, true) : 0;
+    const size_t ws_bytes = general ? carve(probe, nullptr, k, m, block_bytes, 1, true, /*latency=*/true) : 0;
     if (int rc = st.h.ensure(ws_off + ws_bytes + 8)) return rc;
     if (int rc = st.d.ensure(ws_off + ws_bytes + scratch, st.stream)) return rc;
     uint8_t *h = static_cast<uint8_t *>(st.h.p);
@@ -1409,12 +1369,16 @@ extern "C" int cauchy_256_decode(int k, int m, Block *blocks, int block_bytes) {
         // go up with the blocks in one copy, and the recovered rows come back densely (e blocks,
         // no device scatter kernel) to be placed here.
         DecodeWS wh{};
-        carve(wh, h + ws_off, k, m, block_bytes, 1, true);
-        const bool hs = host_decode_setup(wh, k, m, h + data_bytes, e, rec, era);
-        const size_t up = hs ? ws_off + static_cast<size_t>(wh.residual - (h + ws_off)) : data_bytes + k;
+        carve(wh, h + ws_off, k, m, block_bytes, 1, true, /*latency=*/true);
+        SingleGroupOpts sg;
+        sg.slice_scratch = d + ws_off + ws_bytes;
+        sg.h_dense = h;
+        sg.e_dense = e;
+        sg.ws_ext = d + ws_off;
+        sg.host_setup = host_decode_setup(wh, k, m, h + data_bytes, e, rec, era);
+        const size_t up = sg.host_setup ? ws_off + static_cast<size_t>(wh.residual - (h + ws_off)) : data_bytes + k;
         SH_CHECK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, st.stream));
-        const int rc = decode_batch(k, m, block_bytes, 1, d, d + data_bytes, st.stream, nullptr,
-                                    d + ws_off + ws_bytes, h, e, d + ws_off, hs);
+        const int rc = decode_batch(k, m, block_bytes, 1, d, d + data_bytes, st.stream, &sg);
         if (rc != 0) {
             // the staging slot is released on return: nothing queued may still read it
             (void)hipStreamSynchronize(st.stream);
@@ -1431,7 +1395,10 @@ extern "C" int cauchy_256_decode(int k, int m, Block *blocks, int block_bytes) {
     // m == 1 (cauchy_decode_m1) and the parameter-error paths: the batch decode in place
     int *e_host = reinterpret_cast<int *>(h + ((data_bytes + k + 3) & ~static_cast<size_t>(3)));
     *e_host = 0;
-    const int rc = decode_batch(k, m, block_bytes, 1, d, d + data_bytes, st.stream, e_host, d + data_bytes + 256);
+    SingleGroupOpts sg;
+    sg.e_host = e_host;
+    sg.slice_scratch = d + data_bytes + 256;
+    const int rc = decode_batch(k, m, block_bytes, 1, d, d + data_bytes, st.stream, &sg);
     if (rc != 0) {
         (void)hipStreamSynchronize(st.stream);
         return rc;

@@ -215,3 +215,72 @@ int main() {
                                 "512 nq=16 full=0 SSSSSS", "512 nq=16 full=1 ssssss",
                                 "520 nq=20 full=0 SSSSSS", "520 nq=20 full=1 RRVVVV",  # nq 17 -> 20
                                 "1400 nq=44 full=0 SSSSSS", "1400 nq=44 full=1 RRVVVV"]
+
+
+def test_stagea_route_table(tmp_path):
+    """csrc/stagea_route.hpp alone decides which kernel family runs encode and decode stage A. A
+    stand-alone host program prints, per (k, kfix, tile) row, the route of encode and decode with
+    1 and 8 step slices (F compile-time, T tile, G generic; lower case = sliced) and the decode
+    position-table stride. Expected, written out by hand: a compiled kernel runs unless the call is
+    sliced; slicing needs the tile kernels, and in decode also position tables round4(k) wide, so
+    the sliced decode of (150, K = 224) stays on its compile-time kernel."""
+    src = tmp_path / "routes.cpp"
+    src.write_text(r'''
+#include "stagea_route.hpp"
+#include <cstdio>
+int main() {
+    const int rows[][3] = {{200, 200, 1}, {150, 224, 1}, {150, 0, 1}, {200, 200, 0}, {20, 0, 0}};
+    for (const auto &r : rows) {
+        std::printf("%d %d %d ", r[0], r[1], r[2]);
+        int kp = 0;
+        for (int dec = 0; dec < 2; ++dec)
+            for (int slices : {1, 8}) {
+                const sh::StageAPlan p = sh::stagea_route(r[0], r[1], r[2] != 0, dec != 0, slices);
+                const char c = p.route == sh::StageARoute::Fixed ? 'F' : p.route == sh::StageARoute::Tile ? 'T' : 'G';
+                std::putchar(p.sliced ? c - 'A' + 'a' : c);
+                if (dec && kp && kp != p.kp) return 1;  // the stride does not depend on the slices
+                if (dec) kp = p.kp;
+            }
+        std::printf(" kp=%d\n", kp);
+    }
+    return 0;
+}
+''')
+    exe = tmp_path / "routes"
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-std=c++17", "-Wall", "-Werror", f"-I{os.path.join(ROOT, 'shorthair_amd', 'csrc')}",
+                    str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True, timeout=60).stdout
+    # k kfix tile, then encode x1, encode x8, decode x1, decode x8
+    assert out.splitlines() == ["200 200 1 FtFt kp=200",
+                                "150 224 1 FtFF kp=224",  # round4(224) != round4(150): decode not sliced
+                                "150 0 1 TtTt kp=152",    # SH_FORCE_TILE, or no compiled kernel
+                                "200 200 0 FFFF kp=200",  # no slicing without the tile kernels
+                                "20 0 0 GGGG kp=20"]
+
+
+def test_batch_path_table(capfd):
+    """cauchy_256_batch_path is a host-only query (a launcher may ask before it spawns its rank
+    processes): 1 = compile-time kernels, 2 = tile kernels, 0 = generic kernels, -1 = invalid.
+    Expected from the compiled shapes (200,32) (64,16) (28,4) (112,16) (224,32) (200,56) (190,66)
+    (216,40), used down to k = 0.6 K, and the tile kernels' B/8 >= 16, k >= 2, m >= 2. The query
+    must not initialise the GPU."""
+    table = [((200, 32, 1400), 1),   # compiled shape
+             ((150, 32, 1400), 1),   # 150 >= 0.6 x 224
+             ((120, 32, 1400), 1),   # 120 = 0.6 x 200
+             ((119, 32, 1400), 2),   # below every 0.6 K of m = 32
+             ((28, 4, 256), 1),      # compiled shape
+             ((28, 4, 120), 0),      # B/8 = 15 < 16
+             ((50, 10, 1000), 2),    # no compiled kernel, tile kernels usable
+             ((30, 4, 96), 0),       # below the tile kernels
+             ((20, 5, 64), 0),
+             ((10, 1, 1400), 0),     # m < 2
+             ((1, 1, 8), 0),         # k < 2
+             ((200, 57, 1400), -1),  # k + m > 256
+             ((28, 4, 100), -1),     # B % 8 != 0
+             ((0, 4, 64), -1)]       # k < 1
+    import shorthair_amd
+    got = [shorthair_amd.lib.cauchy_256_batch_path(*shape) for shape, _ in table]
+    assert got == [value for _, value in table], list(zip(table, got))
+    # without a GPU an initialisation attempt prints the library's "no HIP device" error
+    assert "libcauchy256" not in capfd.readouterr().err

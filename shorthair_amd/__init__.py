@@ -15,7 +15,9 @@ import os
 __all__ = ["lib", "Block", "CAUCHY_256_VERSION", "cauchy_256_init", "cauchy_256_encode",
            "cauchy_256_decode", "encode_batch", "decode_batch", "decode_batch_out",
            "encode_batch_var", "decode_batch_out_var", "frame_batch", "unframe_batch", "unframe_scratch_bytes", "wire_emit_batch",
-           "UNFRAME_TILE_SLOTS", "UNFRAME_SCAN_PASS", "groups_stats",
+           "rx_list_batch", "rx_list_capacity", "rx_list_scratch_bytes",
+           "UNFRAME_TILE_SLOTS", "UNFRAME_SCAN_PASS", "RX_MAX_PACKETS", "RX_INFO_INTS", "RX_SCAN_TILE", "RX_SCAN_PASS",
+           "groups_stats",
            "fill_synthetic", "erasure_pattern", "batch_reserve", "batch_errors", "has_fixed", "path", "default_stream", "sync", "LIB_PATH",
            "EXPORTED_SYMBOLS"]
 
@@ -38,11 +40,17 @@ EXPORTED_SYMBOLS = [
     "shorthair_groups_stats", "shorthair_groups_set_framing", "shorthair_groups_traffic",
     "shorthair_frame_batch", "shorthair_unframe_scratch_bytes", "shorthair_unframe_batch",
     "shorthair_groups_set_delivery", "shorthair_wire_emit_batch", "shorthair_groups_set_wire",
+    "shorthair_rx_list_capacity", "shorthair_rx_list_scratch_bytes", "shorthair_rx_list_batch",
 ]
 
 # include/shorthair_unframe.h: slots per tile sum, and tile sums the scan workgroup takes per pass
 UNFRAME_TILE_SLOTS = 256
 UNFRAME_SCAN_PASS = 256
+# include/shorthair_rx.h: records per group, ints per d_info entry, groups per lane and per pass of the scan
+RX_MAX_PACKETS = 512
+RX_INFO_INTS = 8
+RX_SCAN_TILE = 16
+RX_SCAN_PASS = 4096
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} not built: run `python shorthair_amd/build.py` "
@@ -93,6 +101,12 @@ lib.shorthair_unframe_batch.argtypes = ([_c.c_int] * 3 + [_c.c_longlong] + [_c.c
 lib.shorthair_unframe_batch.restype = _c.c_int
 lib.shorthair_wire_emit_batch.argtypes = [_c.c_int] * 4 + [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 3
 lib.shorthair_wire_emit_batch.restype = _c.c_int
+lib.shorthair_rx_list_capacity.argtypes = [_c.c_int] * 3
+lib.shorthair_rx_list_capacity.restype = _c.c_int
+lib.shorthair_rx_list_scratch_bytes.argtypes = [_c.c_int] * 2
+lib.shorthair_rx_list_scratch_bytes.restype = _c.c_longlong
+lib.shorthair_rx_list_batch.argtypes = [_c.c_int] * 6 + [_c.c_void_p] * 4 + [_c.c_longlong] + [_c.c_void_p] * 10
+lib.shorthair_rx_list_batch.restype = _c.c_int
 lib.shorthair_groups_stats.argtypes = [_c.c_void_p, _c.c_void_p]
 lib.shorthair_groups_stats.restype = _c.c_int
 lib.cauchy_256_batch_reserve.argtypes = [_c.c_int] * 4
@@ -244,6 +258,43 @@ def wire_emit_batch(k, m, block_bytes, groups, first, total_blocks, recovery, wi
         return t if t is None or isinstance(t, int) else int(t.data_ptr())
     return _check(lib.shorthair_wire_emit_batch(k, m, block_bytes, groups, ptr(first), total_blocks, ptr(recovery),
                                                 ptr(wire), _stream(stream)), "wire_emit_batch")
+
+
+def rx_list_capacity(groups, packets, kmax):
+    """Entries of each list array of rx_list_batch: min(packets, groups * kmax). Host only; raises
+    ValueError on invalid arguments."""
+    n = lib.shorthair_rx_list_capacity(groups, packets, kmax)
+    if n < 0:
+        raise ValueError("rx_list_capacity: bad arguments")
+    return n
+
+
+def rx_list_scratch_bytes(groups, packets):
+    """Bytes of device scratch rx_list_batch needs for (groups, packets). Host only; raises ValueError
+    on invalid arguments."""
+    n = lib.shorthair_rx_list_scratch_bytes(groups, packets)
+    if n < 0:
+        raise ValueError("rx_list_scratch_bytes: bad arguments")
+    return n
+
+
+def rx_list_batch(kmin, kmax, m, block_bytes, groups, packets, pkt_first, pkt_off, pkt_len, ring, ring_bytes,
+                  info, first, slot_group, off, length, raw, rows, summary, scratch, stream=None):
+    """List received packets on the GPU (include/shorthair_rx.h): group g holds the records "[id][c][body]"
+    of pkt_len[p] bytes at ring + pkt_off[p], p in [pkt_first[g], pkt_first[g + 1]). Writes info int32
+    [groups][8] (status, k, m, B, n_orig, n_rec, slot, first_rec), the var-k decode's first int32
+    [groups + 1], slot_group int32 [groups], frame_batch's off int64 / length int32 / raw uint8 and the
+    decode's rows uint8 (each [rx_list_capacity(groups, packets, kmax)]) and summary int32 [8]. pkt_first
+    int32 [groups + 1], pkt_off int64 [packets], pkt_len int32 [packets], ring uint8 [ring_bytes], scratch
+    uint8 [rx_list_scratch_bytes(groups, packets)] (8-byte aligned): cuda tensors, or integer device
+    addresses."""
+    def ptr(t):
+        return t if t is None or isinstance(t, int) else int(t.data_ptr())
+    return _check(lib.shorthair_rx_list_batch(kmin, kmax, m, block_bytes, groups, packets, ptr(pkt_first),
+                                              ptr(pkt_off), ptr(pkt_len), ptr(ring), ring_bytes, ptr(info),
+                                              ptr(first), ptr(slot_group), ptr(off), ptr(length), ptr(raw),
+                                              ptr(rows), ptr(summary), ptr(scratch), _stream(stream)),
+                  "rx_list_batch")
 
 
 def groups_stats():

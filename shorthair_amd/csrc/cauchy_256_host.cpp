@@ -23,6 +23,7 @@
 #include "../../include/cauchy_256.h"
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/shorthair_frame.h"
+#include "../../include/shorthair_rx.h"
 #include "../../include/shorthair_unframe.h"
 #include "../../include/shorthair_wire.h"
 #include "cauchy_math.hpp"
@@ -30,6 +31,7 @@
 #include "frame.hpp"
 #include "kernels.hpp"
 #include "measure.hpp"
+#include "rx_list.hpp"
 #include "stagea_route.hpp"
 #include "unframe.hpp"
 #include "wire.hpp"
@@ -1013,6 +1015,68 @@ extern "C" int shorthair_wire_emit_batch(int k, int m, int block_bytes, int grou
     SH_CHECK(sh::launch_wire_emit(k, m, block_bytes, groups, d_first, total_blocks,
                                   static_cast<const uint8_t *>(d_recovery), static_cast<uint8_t *>(d_wire),
                                   pick(stream)));
+    return 0;
+}
+
+extern "C" int shorthair_rx_list_capacity(int groups, int packets, int kmax) {
+    if (groups < 0 || packets < 0 || kmax < 2 || kmax > 255) return -1;
+    return static_cast<int>(std::min<long long>(packets, static_cast<long long>(groups) * kmax));
+}
+
+extern "C" long long shorthair_rx_list_scratch_bytes(int groups, int packets) {
+    if (groups < 0 || packets < 0) return -1;
+    return sh::rx_list_scratch_bytes(groups, packets);
+}
+
+extern "C" int shorthair_rx_list_batch(int kmin, int kmax, int m, int block_bytes, int groups, int packets,
+                                       const int *d_pkt_first, const long long *d_pkt_off, const int *d_pkt_len,
+                                       const void *d_ring, long long ring_bytes, int *d_info, int *d_first,
+                                       int *d_slot_group, long long *d_off, int *d_len, unsigned char *d_raw,
+                                       unsigned char *d_rows, int *d_summary, void *d_scratch, void *stream) {
+    if (kmin < 2 || kmin > kmax || kmax > 255 || m < 1 || kmax + m > 256) return -1;
+    if (block_bytes < 8 || block_bytes % 8 != 0 || groups < 0 || packets < 0 || ring_bytes < 0) return -1;
+    auto mis = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
+    if (mis(d_pkt_first, 4) || mis(d_pkt_len, 4) || mis(d_info, 4) || mis(d_first, 4) || mis(d_slot_group, 4) ||
+        mis(d_len, 4) || mis(d_summary, 4) || mis(d_pkt_off, 8) || mis(d_off, 8) || mis(d_scratch, 8))
+        return -1;
+    const int capacity = shorthair_rx_list_capacity(groups, packets, kmax);
+    if (groups > 0) {
+        if (!d_pkt_first || !d_info || !d_first || !d_slot_group || !d_summary || !d_scratch) return -1;
+        if (packets > 0 && (!d_pkt_off || !d_pkt_len || !d_ring)) return -1;
+        if (capacity > 0 && (!d_off || !d_len || !d_raw || !d_rows)) return -1;
+    }
+    if (groups == 0) return 0;
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    hipStream_t s = pick(stream);
+    StreamState *st = stream_state(c, s);
+    if (!st) return -2;
+    sh::RxListArgs a{};
+    a.pkt_first = d_pkt_first;
+    a.pkt_off = d_pkt_off;
+    a.pkt_len = d_pkt_len;
+    a.ring = static_cast<const uint8_t *>(d_ring);
+    a.ring_bytes = ring_bytes;
+    a.info = d_info;
+    a.first = d_first;
+    a.slot_group = d_slot_group;
+    a.off = d_off;
+    a.len = d_len;
+    a.raw = d_raw;
+    a.rows = d_rows;
+    a.summary = d_summary;
+    a.errors = st->d_errors;
+    a.kmin = kmin;
+    a.kmax = kmax;
+    a.m = m;
+    a.B = block_bytes;
+    a.groups = groups;
+    a.packets = packets;
+    a.capacity = capacity;
+    // under the stream's lock, like shorthair_frame_batch's count
+    std::lock_guard<std::mutex> g(st->mu);
+    SH_CHECK(sh::launch_rx_list(a, d_scratch, s));
     return 0;
 }
 

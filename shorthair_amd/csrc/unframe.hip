@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/shorthair_unframe.h"
+#include "block_scan.hpp"
 #include "unframe.hpp"
 
 namespace sh {
@@ -44,26 +45,6 @@ struct UnframeArgs {
 };
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-// Inclusive scan over the workgroup's UNFRAME_THREADS values; `total` is their sum.
-template <class T>
-__device__ __forceinline__ T block_scan(T v, T *wsum, T &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    T pre = 0;
-    total = 0;
-    for (int w = 0; w < UNFRAME_THREADS / 64; ++w) {
-        if (w < wave) pre += wsum[w];
-        total += wsum[w];
-    }
-    return pre + x;
-}
 
 // The block of slot s, in blocks from `out`.
 __device__ __forceinline__ long long slot_block(const UnframeArgs &a, uint32_t s) {
@@ -92,7 +73,7 @@ __global__ __launch_bounds__(UNFRAME_THREADS) void unframe_lengths(UnframeArgs a
     }
     const int v = max(len, 0);  // <= 65535: a tile sums to < 2^24
     int total;
-    const int incl = block_scan(v, wsum, total);
+    const int incl = block_scan<UNFRAME_THREADS>(v, wsum, total);
     if (in) a.local[s] = incl - v;
     if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
     // as var_check (kernels.hip): a ballot, then one atomicAdd per wave
@@ -107,7 +88,7 @@ __global__ __launch_bounds__(UNFRAME_THREADS) void unframe_scan(UnframeArgs a) {
         const int t = base + static_cast<int>(threadIdx.x);
         const long long v = t < a.tiles ? a.sums[t] : 0;
         long long total;
-        const long long incl = block_scan(v, wsum, total);
+        const long long incl = block_scan<UNFRAME_THREADS>(v, wsum, total);
         if (t < a.tiles) a.sums[t] = carry + incl - v;
         carry += total;
         __syncthreads();  // wsum is rewritten by the next pass

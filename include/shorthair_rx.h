@@ -17,7 +17,8 @@
  *   recovery   (:614-616)                  id = k + y, c = k - 1, the body is "[m-1][block]"
  *   a record is an original iff id <= c    (OnData :814)
  *
- * Reconstructing the truncated group counter (:774-780) is sequential state; it stays with the caller.
+ * Reconstructing the truncated group counter (:774-780) and sorting the datagrams by group is what
+ * shorthair_rx_group_batch (below) does, on the GPU, for datagrams as they arrive.
  * Group g holds the records p in [d_pkt_first[g], d_pkt_first[g + 1]), in arrival order.
  *
  * Per-group rule, in this order (the result is rx_info's of shorthair_recover_groups on the same
@@ -126,6 +127,112 @@ int shorthair_rx_list_batch(int kmin, int kmax, int m, int block_bytes, int grou
                             int *d_slot_group /* [groups] */, long long *d_off, int *d_len,
                             unsigned char *d_raw, unsigned char *d_rows /* each [capacity] */,
                             int *d_summary /* [8] */, void *d_scratch, void *stream);
+
+/*
+ * shorthair_rx_group_batch -- the stage in front of the listing: datagrams as they arrive, in arrival
+ * order, become the records and the CSR by group that shorthair_rx_list_batch reads (its d_pkt_first,
+ * d_pkt_off and d_pkt_len, with packets = datagrams). The host supplies the (offset, length) pairs its
+ * completion queue reports and one int of state, and reads no header byte.
+ *
+ * Datagram i is the d_dg_len[i] bytes at d_ring + d_dg_off[i], at any alignment, exactly as
+ * ShorthairCodec::Recv (Shorthair.cpp:1192-1211) gets it: "[seq u16]", then one of
+ *
+ *   [g & 0x7f][id][c][body]                  a data datagram (Send :984-1015)
+ *   [0x80 | ...][oob bytes]                  an out-of-band datagram (SendOOB :1036-1055)
+ *   [f with bits 0x80 and 1][seen u32][count u32]
+ *                                            a pong prefix (Tick :1079-1089, OnOOB :664-699), followed by
+ *                                            nothing, by "[0x80 | ...][oob]" or by "[g][id][c][body]"
+ *
+ * d_state_in[0] is the unwrapped group number U of the last data datagram before this batch; U & 255 is
+ * the reference's _last_group. A fresh receiver passes 0. With s7(x) = ((x & 127) ^ 64) - 64:
+ *
+ * Per-datagram rule, in this order:
+ *
+ *   1  malformed (class -1), and nothing of the datagram is read: len < 3, off < 0 or off + len >
+ *      ring_bytes
+ *   2  f = byte 2. If f & 0x80 and f & 1, the datagram carries a pong and 8 is added to its class:
+ *      len < 11 is class -1 after all (OnOOB drops a truncated pong; no 8 is added, and it is not counted
+ *      as carrying a pong); len == 11 is kind 2, pong only; otherwise h = 11, and byte 11 decides: kind 1
+ *      (out of band) when it has bit 0x80, else a data candidate. If f & 0x80 without bit 0: kind 1,
+ *      h = 2. Otherwise a data candidate with h = 2. The out-of-band payload and the record
+ *      "[id][c][body]" both start at off + h + 1
+ *   3  a data candidate's record has len - h - 1 bytes. At most 2: kind 3, short (OnData returns at
+ *      len <= PROTOCOL_OVERHEAD before it touches _last_group, so a short datagram does not move the group
+ *      state). Otherwise it is a data datagram with p = byte h & 127
+ *   4  the data datagrams of step 3, in arrival order: u_i = u_prev + s7(p_i - prev_p), where for the
+ *      first one u_prev = d_state_in[0] and prev_p = d_state_in[0] & 127, and after that u_prev and prev_p
+ *      are the previous data datagram's u and p. u_i & 255 is the code_group of :774-780
+ *      (Counter<u8,8>::ExpandFromTruncated, Counter.h:297-316). u is kept modulo 2^32.
+ *      d_state_out[0] is the last u, or d_state_in[0] if the batch has no data datagram
+ *   5  slot = u_i - d_state_in[0] + back. Outside [0, groups): kind 4, out of window; it has still moved
+ *      the group state in step 4, as it would in the reference. Otherwise kind 0, binned
+ *
+ * Outputs; every element named here is written on every call, and nothing depends on earlier contents:
+ *
+ *   d_dg_class[i]   kind (+ 8 with a pong), or -1
+ *   d_dg_slot[i]    the slot for kind 0, else -1
+ *   d_pkt_first     [groups + 1]: slot s holds the records [d_pkt_first[s], d_pkt_first[s + 1]), the
+ *                   kind-0 datagrams of the slot in arrival order
+ *   d_pkt_off, d_pkt_len, d_pkt_dg
+ *                   per record: dg_off + h + 1, dg_len - h - 1 and the datagram's index i. Entries at or
+ *                   past the record total are 0, 0 and -1
+ *   d_slot_group[s] d_state_in[0] - back + s: the unwrapped group of every slot, so that a caller matches
+ *                   slots across batches without reading the state back
+ *   d_other         the indices of all datagrams that were not binned, ascending; -1 past their count
+ *   d_summary[8]    [0] records binned [1] entries of d_other [2] lowest used slot (groups if none)
+ *                   [3] highest used slot + 1 (0 if none) [4] malformed [5] out of window
+ *                   [6] datagrams carrying a pong (class >= 8) [7] short
+ *
+ * Malformed datagrams add to the stream's error counter (cauchy_256_batch_errors), as the listing's
+ * malformed groups do.
+ *
+ * Arrival order within a slot is exact for every slot with at most SHORTHAIR_RX_MAX_PACKETS records. A
+ * slot with more holds each of its records exactly once, in an unspecified order; the listing rejects
+ * such a group anyway.
+ *
+ * What the call does not do. The loss statistics from the sequence numbers (LossStatistics::Update,
+ * which has a reset branch) stay with the caller. Group time-outs and "ignore the rest of a finished
+ * group" (:783-791) are time and history: the batch looks at all records of a slot, as the listing does.
+ * The listing's limit of SHORTHAIR_RX_MAX_PACKETS records is unchanged. Two slots more than 256 apart
+ * share an 8-bit group number in the reference; here they stay distinct.
+ *
+ * Scratch: shorthair_rx_group_scratch_bytes(datagrams, groups) bytes of device memory at d_scratch
+ * (8-byte aligned), which the call overwrites; > 0 for valid arguments and non-decreasing in both. It
+ * holds a counter per slot, two ints per datagram and eight per tile. The datagrams are scanned in tiles
+ * of SHORTHAIR_RX_GROUP_TILE; one workgroup scans the tile aggregates, SHORTHAIR_RX_GROUP_TILE_PASS tiles
+ * per pass with a running carry, and another the slot counters: each of its lanes sums
+ * SHORTHAIR_RX_GROUP_SLOT_TILE consecutive slots, SHORTHAIR_RX_GROUP_SLOT_PASS slots per pass.
+ *
+ * Host-checked (-1, nothing enqueued, the GPU is not initialised): datagrams, groups and ring_bytes >= 0;
+ * 0 <= back <= groups; d_dg_len, d_state_in, d_state_out, d_dg_class, d_dg_slot, d_pkt_first, d_pkt_len,
+ * d_pkt_dg, d_slot_group, d_other and d_summary 4-byte aligned; d_dg_off, d_pkt_off and d_scratch 8-byte
+ * aligned; when groups > 0, non-null d_state_in, d_state_out, d_pkt_first, d_slot_group, d_summary and
+ * d_scratch, and non-null d_dg_off, d_dg_len, d_ring, d_dg_class, d_dg_slot, d_pkt_off, d_pkt_len,
+ * d_pkt_dg and d_other unless datagrams == 0. groups == 0 returns 0 and touches nothing; datagrams == 0
+ * with groups > 0 writes the empty outputs. There is no limit on groups other than memory.
+ *
+ * Asynchronous on `stream`, like the listing: six kernels, none of which waits on another workgroup; no
+ * host synchronisation, nothing is allocated after the stream's first call into the library, so the call
+ * can be captured into a graph. Return codes: 0 ok, -1 invalid arguments, -2 GPU/runtime error.
+ */
+#define SHORTHAIR_RX_GROUP_TILE 256       /* datagrams per tile of the datagram scans */
+#define SHORTHAIR_RX_GROUP_TILE_PASS 1024 /* tile aggregates the scan workgroup takes per pass */
+#define SHORTHAIR_RX_GROUP_SLOT_TILE 16   /* consecutive slots one lane of the slot scan sums */
+#define SHORTHAIR_RX_GROUP_SLOT_PASS 4096 /* slots the slot scan takes per pass */
+
+/* Bytes of device scratch the call below needs. Host only. -1 on invalid arguments (datagrams < 0,
+ * groups < 0). */
+long long shorthair_rx_group_scratch_bytes(int datagrams, int groups);
+
+int shorthair_rx_group_batch(int datagrams, int groups, int back,
+                             const long long *d_dg_off /* [datagrams] */, const int *d_dg_len /* [datagrams] */,
+                             const void *d_ring, long long ring_bytes,
+                             const int *d_state_in /* [1] */, int *d_state_out /* [1], may alias d_state_in */,
+                             int *d_dg_class /* [datagrams] */, int *d_dg_slot /* [datagrams] */,
+                             int *d_pkt_first /* [groups + 1] */,
+                             long long *d_pkt_off, int *d_pkt_len, int *d_pkt_dg /* each [datagrams] */,
+                             int *d_slot_group /* [groups] */, int *d_other /* [datagrams] */,
+                             int *d_summary /* [8] */, void *d_scratch, void *stream);
 
 #ifdef __cplusplus
 }

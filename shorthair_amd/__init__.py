@@ -16,6 +16,8 @@ __all__ = ["lib", "Block", "CAUCHY_256_VERSION", "cauchy_256_init", "cauchy_256_
            "cauchy_256_decode", "encode_batch", "decode_batch", "decode_batch_out",
            "encode_batch_var", "decode_batch_out_var", "frame_batch", "unframe_batch", "unframe_scratch_bytes", "wire_emit_batch",
            "rx_list_batch", "rx_list_capacity", "rx_list_scratch_bytes",
+           "rx_group_batch", "rx_group_scratch_bytes",
+           "RX_GROUP_TILE", "RX_GROUP_TILE_PASS", "RX_GROUP_SLOT_TILE", "RX_GROUP_SLOT_PASS",
            "UNFRAME_TILE_SLOTS", "UNFRAME_SCAN_PASS", "RX_MAX_PACKETS", "RX_INFO_INTS", "RX_SCAN_TILE", "RX_SCAN_PASS",
            "groups_stats",
            "fill_synthetic", "erasure_pattern", "batch_reserve", "batch_errors", "has_fixed", "path", "default_stream", "sync", "LIB_PATH",
@@ -41,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "shorthair_frame_batch", "shorthair_unframe_scratch_bytes", "shorthair_unframe_batch",
     "shorthair_groups_set_delivery", "shorthair_wire_emit_batch", "shorthair_groups_set_wire",
     "shorthair_rx_list_capacity", "shorthair_rx_list_scratch_bytes", "shorthair_rx_list_batch",
+    "shorthair_rx_group_scratch_bytes", "shorthair_rx_group_batch",
 ]
 
 # include/shorthair_unframe.h: slots per tile sum, and tile sums the scan workgroup takes per pass
@@ -51,6 +54,12 @@ RX_MAX_PACKETS = 512
 RX_INFO_INTS = 8
 RX_SCAN_TILE = 16
 RX_SCAN_PASS = 4096
+# include/shorthair_rx.h: datagrams per tile of rx_group_batch, tiles per pass of its tile scan, slots per lane
+# and per pass of its slot scan
+RX_GROUP_TILE = 256
+RX_GROUP_TILE_PASS = 1024
+RX_GROUP_SLOT_TILE = 16
+RX_GROUP_SLOT_PASS = 4096
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} not built: run `python shorthair_amd/build.py` "
@@ -107,6 +116,10 @@ lib.shorthair_rx_list_scratch_bytes.argtypes = [_c.c_int] * 2
 lib.shorthair_rx_list_scratch_bytes.restype = _c.c_longlong
 lib.shorthair_rx_list_batch.argtypes = [_c.c_int] * 6 + [_c.c_void_p] * 4 + [_c.c_longlong] + [_c.c_void_p] * 10
 lib.shorthair_rx_list_batch.restype = _c.c_int
+lib.shorthair_rx_group_scratch_bytes.argtypes = [_c.c_int] * 2
+lib.shorthair_rx_group_scratch_bytes.restype = _c.c_longlong
+lib.shorthair_rx_group_batch.argtypes = [_c.c_int] * 3 + [_c.c_void_p] * 3 + [_c.c_longlong] + [_c.c_void_p] * 13
+lib.shorthair_rx_group_batch.restype = _c.c_int
 lib.shorthair_groups_stats.argtypes = [_c.c_void_p, _c.c_void_p]
 lib.shorthair_groups_stats.restype = _c.c_int
 lib.cauchy_256_batch_reserve.argtypes = [_c.c_int] * 4
@@ -295,6 +308,34 @@ def rx_list_batch(kmin, kmax, m, block_bytes, groups, packets, pkt_first, pkt_of
                                               ptr(first), ptr(slot_group), ptr(off), ptr(length), ptr(raw),
                                               ptr(rows), ptr(summary), ptr(scratch), _stream(stream)),
                   "rx_list_batch")
+
+
+def rx_group_scratch_bytes(datagrams, groups):
+    """Bytes of device scratch rx_group_batch needs for (datagrams, groups). Host only; raises ValueError
+    on invalid arguments."""
+    n = lib.shorthair_rx_group_scratch_bytes(datagrams, groups)
+    if n < 0:
+        raise ValueError("rx_group_scratch_bytes: bad arguments")
+    return n
+
+
+def rx_group_batch(datagrams, groups, back, dg_off, dg_len, ring, ring_bytes, state_in, state_out, dg_class, dg_slot,
+                   pkt_first, pkt_off, pkt_len, pkt_dg, slot_group, other, summary, scratch, stream=None):
+    """Group received datagrams on the GPU (include/shorthair_rx.h): datagram i is the dg_len[i] bytes
+    "[seq u16][pong prefix?][g & 0x7f][id][c][body]" at ring + dg_off[i], in arrival order; state_in int32 [1]
+    is the unwrapped group number before the batch. Writes state_out int32 [1] (may be state_in), dg_class
+    and dg_slot int32 [datagrams], rx_list_batch's pkt_first int32 [groups + 1], pkt_off int64 and pkt_len
+    int32 [datagrams], pkt_dg int32 [datagrams], slot_group int32 [groups], other int32 [datagrams] and
+    summary int32 [8]. dg_off int64 [datagrams], dg_len int32 [datagrams], ring uint8 [ring_bytes], scratch
+    uint8 [rx_group_scratch_bytes(datagrams, groups)] (8-byte aligned): cuda tensors, or integer device
+    addresses."""
+    def ptr(t):
+        return t if t is None or isinstance(t, int) else int(t.data_ptr())
+    return _check(lib.shorthair_rx_group_batch(datagrams, groups, back, ptr(dg_off), ptr(dg_len), ptr(ring), ring_bytes,
+                                               ptr(state_in), ptr(state_out), ptr(dg_class), ptr(dg_slot),
+                                               ptr(pkt_first), ptr(pkt_off), ptr(pkt_len), ptr(pkt_dg),
+                                               ptr(slot_group), ptr(other), ptr(summary), ptr(scratch),
+                                               _stream(stream)), "rx_group_batch")
 
 
 def groups_stats():

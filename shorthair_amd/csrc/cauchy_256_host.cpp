@@ -31,6 +31,7 @@
 #include "frame.hpp"
 #include "kernels.hpp"
 #include "measure.hpp"
+#include "rx_group.hpp"
 #include "rx_list.hpp"
 #include "stagea_route.hpp"
 #include "unframe.hpp"
@@ -1077,6 +1078,62 @@ extern "C" int shorthair_rx_list_batch(int kmin, int kmax, int m, int block_byte
     // under the stream's lock, like shorthair_frame_batch's count
     std::lock_guard<std::mutex> g(st->mu);
     SH_CHECK(sh::launch_rx_list(a, d_scratch, s));
+    return 0;
+}
+
+extern "C" long long shorthair_rx_group_scratch_bytes(int datagrams, int groups) {
+    if (datagrams < 0 || groups < 0) return -1;
+    return sh::rx_group_scratch_bytes(datagrams, groups);
+}
+
+extern "C" int shorthair_rx_group_batch(int datagrams, int groups, int back, const long long *d_dg_off,
+                                        const int *d_dg_len, const void *d_ring, long long ring_bytes,
+                                        const int *d_state_in, int *d_state_out, int *d_dg_class, int *d_dg_slot,
+                                        int *d_pkt_first, long long *d_pkt_off, int *d_pkt_len, int *d_pkt_dg,
+                                        int *d_slot_group, int *d_other, int *d_summary, void *d_scratch,
+                                        void *stream) {
+    if (datagrams < 0 || groups < 0 || back < 0 || back > groups || ring_bytes < 0) return -1;
+    auto mis = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
+    if (mis(d_dg_len, 4) || mis(d_state_in, 4) || mis(d_state_out, 4) || mis(d_dg_class, 4) || mis(d_dg_slot, 4) ||
+        mis(d_pkt_first, 4) || mis(d_pkt_len, 4) || mis(d_pkt_dg, 4) || mis(d_slot_group, 4) || mis(d_other, 4) ||
+        mis(d_summary, 4) || mis(d_dg_off, 8) || mis(d_pkt_off, 8) || mis(d_scratch, 8))
+        return -1;
+    if (groups > 0) {
+        if (!d_state_in || !d_state_out || !d_pkt_first || !d_slot_group || !d_summary || !d_scratch) return -1;
+        if (datagrams > 0 && (!d_dg_off || !d_dg_len || !d_ring || !d_dg_class || !d_dg_slot || !d_pkt_off ||
+                              !d_pkt_len || !d_pkt_dg || !d_other))
+            return -1;
+    }
+    if (groups == 0) return 0;
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    hipStream_t s = pick(stream);
+    StreamState *st = stream_state(c, s);
+    if (!st) return -2;
+    sh::RxGroupArgs a{};
+    a.dg_off = d_dg_off;
+    a.dg_len = d_dg_len;
+    a.ring = static_cast<const uint8_t *>(d_ring);
+    a.ring_bytes = ring_bytes;
+    a.state_in = d_state_in;
+    a.state_out = d_state_out;
+    a.dg_class = d_dg_class;
+    a.dg_slot = d_dg_slot;
+    a.pkt_first = d_pkt_first;
+    a.pkt_off = d_pkt_off;
+    a.pkt_len = d_pkt_len;
+    a.pkt_dg = d_pkt_dg;
+    a.slot_group = d_slot_group;
+    a.other = d_other;
+    a.summary = d_summary;
+    a.errors = st->d_errors;
+    a.datagrams = datagrams;
+    a.groups = groups;
+    a.back = back;
+    // under the stream's lock, like the listing's count
+    std::lock_guard<std::mutex> g(st->mu);
+    SH_CHECK(sh::launch_rx_group(a, d_scratch, s));
     return 0;
 }
 

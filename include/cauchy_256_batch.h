@@ -15,6 +15,15 @@
  *   rows      [groups][k]                   decode rows (the Block.row fields)
  *
  * Return codes: 0 ok, -1 invalid parameters (as the reference), -2 GPU/runtime error.
+ *
+ * Large blocks. Any block_bytes % 8 == 0 is coded, as by the reference. The compile-time and tile
+ * kernels address a workgroup's groups through 32-bit offsets below 2 GiB, which holds while
+ *   n * max(k, m) * block_bytes <= 0x7FFFFFFF,  n = 511 / nq + 2,
+ *   nq = block_bytes / 8 bytes in 4-byte columns, rounded up to a multiple of 4
+ * (from block_bytes = 16,264 on: 2 * max(k, m) * block_bytes <= 0x7FFFFFFF; smaller blocks always
+ * fit). Shapes past this bound run the generic kernels (64-bit addresses) in every call of this
+ * header and in the single-group cauchy_256_encode / cauchy_256_decode, and cauchy_256_batch_path
+ * reports 0 for them. The bound looks at (k, m, block_bytes) alone, never at `groups`.
  */
 #ifndef SH_AMD_CAUCHY_256_BATCH_H
 #define SH_AMD_CAUCHY_256_BATCH_H
@@ -119,7 +128,8 @@ int cauchy_256_erasure_pattern(unsigned long long g, int k, int m, unsigned long
 /* Which kernels code (k, m, block_bytes): 1 = compile-time-scheduled (generated for this (k, m), or
  * for a larger K of the same m with k >= 0.6 K, whose steps past k then read zeros),
  * 2 = the runtime-coefficient tile kernels (any other (k, m) with block_bytes/8 >= 16),
- * 0 = the generic per-column kernels (shorter blocks), -1 = invalid parameters. Host-only: never
+ * 0 = the generic per-column kernels (shorter blocks, and blocks past the 2 GiB span bound at the
+ * top of this header), -1 = invalid parameters. Host-only: never
  * initialises the GPU. Before the library is initialised, 2 assumes the snippet table loaded
  * inside one 4 GB page (checked at launch, generic kernels otherwise); afterwards it includes it. */
 int cauchy_256_batch_path(int k, int m, int block_bytes);

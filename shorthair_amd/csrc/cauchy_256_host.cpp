@@ -502,7 +502,8 @@ int latency_slices(int nsteps) {
 sh::StageAPlan stage_a_plan(int k, int m, int B, bool tile, bool dec, bool latency) {
     static const bool force_tile = SH_MEASURE_ENV("SH_FORCE_TILE") != nullptr;
     const int slices = latency ? latency_slices(dec ? k + m : k) : 1;
-    return sh::stagea_route(k, force_tile ? 0 : sh::fixed_kernel_k(k, m, B), tile, dec, slices);
+    return sh::stagea_route(k, force_tile ? 0 : sh::fixed_kernel_k(k, m, B), tile, dec, slices,
+                            sh::stagea_span_fits(k, m, B));
 }
 
 // One pass of the tile kernels over the batch (encode, or decode stage A with position tables).

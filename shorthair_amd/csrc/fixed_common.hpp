@@ -180,6 +180,10 @@ __device__ __forceinline__ int var_window(const FixedArgs &a, int g_first, int k
 
 // Var-k batches: offset of group gx's first block from the window f0 (OOR: malformed, outside the
 // workgroup's columns (`in` false), or ending past the descriptor's 2 GiB) and its k (0 then).
+// The host routes every shape with groups_per_wg * kmax * B > 0x7FFFFFFF to the generic kernels
+// (stagea_span_fits, stagea_route.hpp), and a tile's well-formed groups are consecutive blocks, so
+// the 2 GiB test below is reachable only where malformed groups make first[] jump inside a tile
+// (include/cauchy_256_batch.h says what the groups beyond the jump then read).
 __device__ __forceinline__ uint32_t var_base(const FixedArgs &a, int gx, bool in, int kmax, int f0, int &kg) {
     int f = 0;
     kg = 0;

@@ -79,9 +79,12 @@ def _ks(kmax, groups, seed, uniform=False):
 
 
 class Case:
-    """One batch: per-group inputs, the oracle's recovery blocks and one decode pattern per group."""
+    """One batch: per-group inputs, the oracle's recovery blocks and one decode pattern per group.
+    es: the erasure count of every group instead of the drawn ones. force_rows: {group: recovery
+    rows that group's pattern must use}; its e is drawn from their number up. Without the two, a
+    case holds the bytes it always held."""
 
-    def __init__(self, kmax, m, B, groups, seed, uniform=False, ks=None):
+    def __init__(self, kmax, m, B, groups, seed, uniform=False, ks=None, es=None, force_rows=None):
         ora = po.oracle()
         self.kmax, self.m, self.B, self.G = kmax, m, B, groups
         self.ks = ks if ks is not None else _ks(kmax, groups, seed, uniform)
@@ -115,9 +118,20 @@ class Case:
                 self.count[g] = -1
                 continue
             top = min(k, m)
-            e = 0 if g == 3 else (top if g in (0, 1) else int(rng.integers(0, top + 1)))
+            forced = sorted((force_rows or {}).get(g, ()))
+            if es is not None:
+                e = int(es[g])
+                assert len(forced) <= e <= top
+            elif forced:
+                e = int(rng.integers(len(forced), top + 1))
+            else:
+                e = 0 if g == 3 else (top if g in (0, 1) else int(rng.integers(0, top + 1)))
             lost = set(int(x) for x in rng.choice(k, size=e, replace=False))
-            ys = sorted(int(y) for y in rng.choice(m, size=e, replace=False))
+            if forced:
+                free = [y for y in range(m) if y not in forced]
+                ys = sorted(forced + [int(y) for y in rng.choice(free, size=e - len(forced), replace=False)])
+            else:
+                ys = sorted(int(y) for y in rng.choice(m, size=e, replace=False))
             items = [(x, self.data[g][x]) for x in range(k) if x not in lost] + [(k + y, self.rec[g][y]) for y in ys]
             order = rng.permutation(k)
             items = [items[i] for i in order]

@@ -17,6 +17,8 @@ __all__ = ["lib", "Block", "CAUCHY_256_VERSION", "cauchy_256_init", "cauchy_256_
            "encode_batch_var", "decode_batch_out_var", "frame_batch", "unframe_batch", "unframe_scratch_bytes", "wire_emit_batch",
            "rx_list_batch", "rx_list_capacity", "rx_list_scratch_bytes",
            "rx_group_batch", "rx_group_scratch_bytes",
+           "tx_datagram_batch", "tx_datagram_scratch_bytes", "tx_datagram_capacity", "TxGroupDesc",
+           "TX_TILE", "TX_TILE_PASS", "TX_MAX_BLOCK_BYTES", "TX_MAX_DATAGRAM_BYTES",
            "RX_GROUP_TILE", "RX_GROUP_TILE_PASS", "RX_GROUP_SLOT_TILE", "RX_GROUP_SLOT_PASS",
            "UNFRAME_TILE_SLOTS", "UNFRAME_SCAN_PASS", "RX_MAX_PACKETS", "RX_INFO_INTS", "RX_SCAN_TILE", "RX_SCAN_PASS",
            "groups_stats",
@@ -44,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "shorthair_groups_set_delivery", "shorthair_wire_emit_batch", "shorthair_groups_set_wire",
     "shorthair_rx_list_capacity", "shorthair_rx_list_scratch_bytes", "shorthair_rx_list_batch",
     "shorthair_rx_group_scratch_bytes", "shorthair_rx_group_batch",
+    "shorthair_tx_datagram_scratch_bytes", "shorthair_tx_datagram_capacity", "shorthair_tx_datagram_batch",
 ]
 
 # include/shorthair_unframe.h: slots per tile sum, and tile sums the scan workgroup takes per pass
@@ -60,6 +63,12 @@ RX_GROUP_TILE = 256
 RX_GROUP_TILE_PASS = 1024
 RX_GROUP_SLOT_TILE = 16
 RX_GROUP_SLOT_PASS = 4096
+# include/shorthair_tx.h: datagrams per tile of tx_datagram_batch, tiles per pass of its tile scan, the largest
+# recovery block and the largest datagram
+TX_TILE = 256
+TX_TILE_PASS = 1024
+TX_MAX_BLOCK_BYTES = 65544
+TX_MAX_DATAGRAM_BYTES = 65550
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} not built: run `python shorthair_amd/build.py` "
@@ -120,6 +129,15 @@ lib.shorthair_rx_group_scratch_bytes.argtypes = [_c.c_int] * 2
 lib.shorthair_rx_group_scratch_bytes.restype = _c.c_longlong
 lib.shorthair_rx_group_batch.argtypes = [_c.c_int] * 3 + [_c.c_void_p] * 3 + [_c.c_longlong] + [_c.c_void_p] * 13
 lib.shorthair_rx_group_batch.restype = _c.c_int
+lib.shorthair_tx_datagram_scratch_bytes.argtypes = [_c.c_int]
+lib.shorthair_tx_datagram_scratch_bytes.restype = _c.c_longlong
+lib.shorthair_tx_datagram_capacity.argtypes = [_c.c_int] * 3
+lib.shorthair_tx_datagram_capacity.restype = _c.c_longlong
+lib.shorthair_tx_datagram_batch.argtypes = ([_c.c_int] * 4 + [_c.c_void_p] * 2 + [_c.c_int, _c.c_void_p, _c.c_longlong] +
+                                            [_c.c_void_p] * 3 + [_c.c_longlong, _c.c_void_p, _c.c_int] +
+                                            [_c.c_void_p] * 2 + [_c.c_int] + [_c.c_void_p] * 2 +
+                                            [_c.c_int, _c.c_void_p, _c.c_longlong] + [_c.c_void_p] * 6)
+lib.shorthair_tx_datagram_batch.restype = _c.c_int
 lib.shorthair_groups_stats.argtypes = [_c.c_void_p, _c.c_void_p]
 lib.shorthair_groups_stats.restype = _c.c_int
 lib.cauchy_256_batch_reserve.argtypes = [_c.c_int] * 4
@@ -336,6 +354,52 @@ def rx_group_batch(datagrams, groups, back, dg_off, dg_len, ring, ring_bytes, st
                                                ptr(pkt_first), ptr(pkt_off), ptr(pkt_len), ptr(pkt_dg),
                                                ptr(slot_group), ptr(other), ptr(summary), ptr(scratch),
                                                _stream(stream)), "rx_group_batch")
+
+
+class TxGroupDesc(ctypes.Structure):
+    """ShorthairTxGroupDesc (include/shorthair_tx.h): 16 bytes; as numpy, dtype [("rec_off", "<i8"), ("m", "<i4"),
+    ("block_bytes", "<i4")]."""
+    _fields_ = [("rec_off", ctypes.c_longlong), ("m", ctypes.c_int), ("block_bytes", ctypes.c_int)]
+
+
+def tx_datagram_scratch_bytes(datagrams):
+    """Bytes of device scratch tx_datagram_batch needs. Host only; raises ValueError on invalid arguments."""
+    n = lib.shorthair_tx_datagram_scratch_bytes(datagrams)
+    if n < 0:
+        raise ValueError("tx_datagram_scratch_bytes: bad arguments")
+    return n
+
+
+def tx_datagram_capacity(datagrams, max_datagram_bytes, align):
+    """Ring bytes that always suffice for `datagrams` datagrams of at most max_datagram_bytes placed at
+    multiples of align. Host only; raises ValueError on invalid arguments."""
+    n = lib.shorthair_tx_datagram_capacity(datagrams, max_datagram_bytes, align)
+    if n < 0:
+        raise ValueError("tx_datagram_capacity: bad arguments")
+    return n
+
+
+def tx_datagram_batch(datagrams, groups, m, block_bytes, sched, first, total_blocks, payload, payload_bytes, off,
+                      length, recovery, recovery_bytes, group, n_pong, pong_at, pong_val, advance, state_in,
+                      state_out, align, ring, ring_bytes, dg_off, dg_len, dg_class, summary, scratch, stream=None):
+    """Write datagrams in send order on the GPU (include/shorthair_tx.h): entry sched[i] = -1 (a hole),
+    g << 9 | x (original x of slot g) or g << 9 | 256 | y (recovery block y of slot g) becomes
+    "[seq u16][pong prefix?][g & 0x7f][id][c][body]" at ring + dg_off[i], dg_off the exclusive sum of the lengths
+    rounded up to align. sched int32 [datagrams], first int32 [groups + 1], payload uint8 [payload_bytes], off
+    int64 and length int32 [total_blocks], recovery uint8 [recovery_bytes] (8-byte aligned) or None, group
+    [groups] of TxGroupDesc (16 bytes each) or None, pong_at int32 [n_pong], pong_val uint32 [2 * n_pong],
+    state_in and state_out int32 [2] (may be the same), ring uint8 [ring_bytes], dg_off int64 [datagrams + 1],
+    dg_len and dg_class int32 [datagrams], summary int32 [8], scratch uint8
+    [tx_datagram_scratch_bytes(datagrams)] (8-byte aligned): cuda tensors, or integer device addresses."""
+    def ptr(t):
+        return t if t is None or isinstance(t, int) else int(t.data_ptr())
+    return _check(lib.shorthair_tx_datagram_batch(datagrams, groups, m, block_bytes, ptr(sched), ptr(first),
+                                                  total_blocks, ptr(payload), payload_bytes, ptr(off), ptr(length),
+                                                  ptr(recovery), recovery_bytes, ptr(group), n_pong, ptr(pong_at),
+                                                  ptr(pong_val), advance, ptr(state_in), ptr(state_out), align,
+                                                  ptr(ring), ring_bytes, ptr(dg_off), ptr(dg_len), ptr(dg_class),
+                                                  ptr(summary), ptr(scratch), _stream(stream)),
+                  "tx_datagram_batch")
 
 
 def groups_stats():

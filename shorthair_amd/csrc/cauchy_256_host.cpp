@@ -24,6 +24,7 @@
 #include "../../include/cauchy_256_batch.h"
 #include "../../include/shorthair_frame.h"
 #include "../../include/shorthair_rx.h"
+#include "../../include/shorthair_tx.h"
 #include "../../include/shorthair_unframe.h"
 #include "../../include/shorthair_wire.h"
 #include "cauchy_math.hpp"
@@ -34,6 +35,7 @@
 #include "rx_group.hpp"
 #include "rx_list.hpp"
 #include "stagea_route.hpp"
+#include "tx_datagram.hpp"
 #include "unframe.hpp"
 #include "wire.hpp"
 
@@ -1135,6 +1137,81 @@ extern "C" int shorthair_rx_group_batch(int datagrams, int groups, int back, con
     // under the stream's lock, like the listing's count
     std::lock_guard<std::mutex> g(st->mu);
     SH_CHECK(sh::launch_rx_group(a, d_scratch, s));
+    return 0;
+}
+
+extern "C" long long shorthair_tx_datagram_scratch_bytes(int datagrams) {
+    if (datagrams < 0) return -1;
+    return sh::tx_datagram_scratch_bytes(datagrams);
+}
+
+extern "C" long long shorthair_tx_datagram_capacity(int datagrams, int max_datagram_bytes, int align) {
+    if (datagrams < 0 || max_datagram_bytes < 0 || align < 1 || align > 4096 || (align & (align - 1))) return -1;
+    const long long each = (static_cast<long long>(max_datagram_bytes) + align - 1) & ~static_cast<long long>(align - 1);
+    return datagrams * each;
+}
+
+extern "C" int shorthair_tx_datagram_batch(int datagrams, int groups, int m, int block_bytes, const int *d_sched,
+                                           const int *d_first, int total_blocks, const void *d_payload,
+                                           long long payload_bytes, const long long *d_off, const int *d_len,
+                                           const void *d_recovery, long long recovery_bytes,
+                                           const ShorthairTxGroupDesc *d_group, int n_pong, const int *d_pong_at,
+                                           const unsigned *d_pong_val, int advance, const int *d_state_in,
+                                           int *d_state_out, int align, void *d_ring, long long ring_bytes,
+                                           long long *d_dg_off, int *d_dg_len, int *d_dg_class, int *d_summary,
+                                           void *d_scratch, void *stream) {
+    if (datagrams < 0 || groups < 0 || groups > (1 << 22) || m < 0 || block_bytes < 0 || total_blocks < 0) return -1;
+    if (payload_bytes < 0 || recovery_bytes < 0 || ring_bytes < 0 || n_pong < 0 || advance < 0) return -1;
+    if (align < 1 || align > 4096 || (align & (align - 1))) return -1;
+    auto mis = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
+    if (mis(d_sched, 4) || mis(d_first, 4) || mis(d_len, 4) || mis(d_pong_at, 4) || mis(d_pong_val, 4) ||
+        mis(d_state_in, 4) || mis(d_state_out, 4) || mis(d_dg_len, 4) || mis(d_dg_class, 4) || mis(d_summary, 4) ||
+        mis(d_off, 8) || mis(d_group, 8) || mis(d_recovery, 8) || mis(d_dg_off, 8) || mis(d_scratch, 8))
+        return -1;
+    if (!d_state_in || !d_state_out || !d_dg_off || !d_summary || !d_scratch) return -1;
+    if (datagrams > 0 && (!d_sched || !d_dg_len || !d_dg_class)) return -1;
+    if (groups > 0 && !d_first) return -1;
+    if (total_blocks > 0 && (!d_off || !d_len)) return -1;
+    if ((payload_bytes > 0 && !d_payload) || (recovery_bytes > 0 && !d_recovery) || (ring_bytes > 0 && !d_ring)) return -1;
+    if (n_pong > 0 && (!d_pong_at || !d_pong_val)) return -1;
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    hipStream_t s = pick(stream);
+    StreamState *st = stream_state(c, s);
+    if (!st) return -2;
+    sh::TxDatagramArgs a{};
+    a.sched = d_sched;
+    a.first = d_first;
+    a.payload = static_cast<const uint8_t *>(d_payload);
+    a.payload_bytes = payload_bytes;
+    a.off = d_off;
+    a.len = d_len;
+    a.recovery = static_cast<const uint8_t *>(d_recovery);
+    a.recovery_bytes = recovery_bytes;
+    a.group = d_group;
+    a.pong_at = d_pong_at;
+    a.pong_val = d_pong_val;
+    a.state_in = d_state_in;
+    a.state_out = d_state_out;
+    a.ring = static_cast<uint8_t *>(d_ring);
+    a.ring_bytes = ring_bytes;
+    a.dg_off = d_dg_off;
+    a.dg_len = d_dg_len;
+    a.dg_class = d_dg_class;
+    a.summary = d_summary;
+    a.errors = st->d_errors;
+    a.datagrams = datagrams;
+    a.groups = groups;
+    a.m = m;
+    a.B = block_bytes;
+    a.total = total_blocks;
+    a.n_pong = n_pong;
+    a.advance = advance;
+    a.align = align;
+    // under the stream's lock, like shorthair_frame_batch's count
+    std::lock_guard<std::mutex> g(st->mu);
+    SH_CHECK(sh::launch_tx_datagram(a, d_scratch, s));
     return 0;
 }
 

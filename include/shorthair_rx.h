@@ -234,6 +234,122 @@ int shorthair_rx_group_batch(int datagrams, int groups, int back,
                              int *d_slot_group /* [groups] */, int *d_other /* [datagrams] */,
                              int *d_summary /* [8] */, void *d_scratch, void *stream);
 
+/*
+ * shorthair_rx_window_batch -- what a receiver keeps between two batches: the records of the groups that
+ * are still open, and which groups are done (Decoder::OnData ignores the rest of a finished group,
+ * Shorthair.cpp:783-791, IsDone). It runs between the group call and the listing:
+ *
+ *   group(new datagrams) -> window(prev window, prev d_info, new records) -> list -> frame -> decode -> unframe
+ *
+ * A window is `groups` slots of consecutive unwrapped group numbers: slot s is group *base + s. Per slot it
+ * holds the records of its open group in arrival order, as a CSR like the group call's, and a done code.
+ * The caller owns two windows and alternates them as prev and next. The next window's first, off and len
+ * are exactly shorthair_rx_list_batch's d_pkt_first, d_pkt_off and d_pkt_len, with packets = capacity.
+ * ShorthairRxWindow is a host struct of device pointers, read on the host at the call.
+ *
+ * All group arithmetic is on 32-bit wrapped values compared by signed difference. Rule, in this order:
+ *
+ *   1  Base. Gb = d_slot_group[0]; P = *prev->base. N = Gb for a fresh receiver (prev == NULL), else
+ *      N = P + max(0, Gb - P): the window never moves back, so a done code is never lost. *next->base = N
+ *   2  Old slots (prev != NULL). Old slot so has the records [prev->first[so], prev->first[so + 1]). Its
+ *      finished flag f is 2 if any of the n_info arrays has status -1 for so; else 1 if any has status 1 or
+ *      2, or status 0 with k >= 1 and n_orig >= k (all originals seen, :851-857); else 0. d =
+ *      prev->done[so] if that is non-zero, else f. The arrays are the d_info outputs of the listing calls
+ *      that ran over prev's arrays; n_info == 0 finishes nothing. The new slot is s = so - (N - P). Inside
+ *      [0, groups): next->done[s] = d, and if d == 0 the slot's records are carried, with dg = -1. Outside:
+ *      the slot expires, and counts in d_summary[4] if d == 0 and prev->first[so + 1] > prev->first[so]
+ *      (nothing else of an expiring slot is read). This takes the place of the reference's GROUP_TIMEOUT: a
+ *      group leaves when the window's base passes it, not after a time. New slots that no old slot maps to
+ *      are open and empty. d_summary[3] counts the old slots, expiring or not, with prev->done[so] == 0 and
+ *      f == 1
+ *   3  New records. Slot t of the group call, with the records [d_pkt_first[t], d_pkt_first[t + 1]), maps
+ *      to s = t - (N - Gb). s < 0: below the window, dropped and counted in [6]. next->done[s] != 0 (from
+ *      step 2, or made malformed by step 4 on the carried side): ignored, as :787-791 does, and counted in
+ *      [5]. Else they are appended behind the slot's carried records in their own order, with dg from
+ *      d_pkt_dg
+ *   4  Malformed input. A span is malformed if its start is below 0, its end before its start, or its end
+ *      past prev->capacity (of prev) or past `datagrams` (of the group call). A carried record is malformed
+ *      if len < 0, off < 0 or off + len > ring_bytes. A slot that would carry such a span or record, or an
+ *      open slot whose new span is malformed, is malformed: it gets no records and done = 2, and adds one
+ *      to the stream's error counter (cauchy_256_batch_errors) and to [7]. A malformed new span of a slot
+ *      that is below the window or not open counts nothing. Nothing out of bounds is ever read
+ *   5  Placement. Slots take their records in ascending s: next->first[0] = 0, next->first[groups] the
+ *      total. With hold_bytes > 0, carried record r is copied to d_ring + hold_off + (the exclusive sum of
+ *      len rounded up to SHORTHAIR_RX_HOLD_ALIGN over the carried records before it), and its off is that
+ *      place. New records keep their offsets. With hold_bytes == 0 nothing is copied and carried records
+ *      keep their offsets; the caller then keeps the bytes alive
+ *   6  Overflow. The first slot whose records would end past next->capacity, or whose carried bytes -- the
+ *      rounded sum including its own records -- would end past hold_bytes (when hold_bytes > 0), and every
+ *      later slot that has a record, is emptied and gets done = 3; each adds one to the error counter and
+ *      to [7]
+ *   7  Tail. Entries of off, len and dg at or past the total are 0, 0 and -1
+ *   8  Writes. Every named output element is written on every call. prev, the info arrays and the group
+ *      call's outputs are only read. Of d_ring, exactly the carried records' bytes inside [hold_off,
+ *      hold_off + hold_bytes) are written; pad bytes and everything else are left alone, and no byte is
+ *      written twice
+ *
+ * d_summary[8] (64-bit): [0] records in the next window [1] carried records [2] hold bytes used (the
+ * rounded sum) [3] slots newly finished [4] open slots that expired [5] new records ignored [6] new
+ * records below the window [7] slots made malformed or emptied.
+ *
+ * Source lifetime. prev's records are the sources: they lie in the previous hold region and the previous
+ * batch's ring region. Both must stay intact until the call has run, and must not overlap the hold region
+ * that is written. Reach of a load: a load may reach up to 7 bytes past (or, at the ring's end, before) a
+ * record shorter than 8 bytes; it never leaves [0, ring_bytes), and what it reaches outside the record is
+ * masked away.
+ *
+ * Delivering originals. The caller delivers the records of the next window that have dg >= 0 and id <= c:
+ * what OnData delivers on arrival. Carried records (dg == -1) were delivered in their own batch.
+ *
+ * Scratch: shorthair_rx_window_scratch_bytes(groups, capacity) bytes of device memory at d_scratch (8-byte
+ * aligned), which the call overwrites, for `capacity` the larger of the two windows' capacities; > 0 for
+ * valid arguments and non-decreasing in both. It holds seven ints per slot and forty bytes per 256 slots;
+ * nothing is kept per record today. One workgroup scans the slots' (records, bytes) pairs: each of its lanes sums
+ * SHORTHAIR_RX_WINDOW_SCAN_TILE consecutive slots, SHORTHAIR_RX_WINDOW_SCAN_PASS slots per pass with a
+ * running carry.
+ *
+ * Host-checked (-1, nothing enqueued, the GPU is not initialised): groups, datagrams and both capacities
+ * >= 0; next non-null; 0 <= n_info <= SHORTHAIR_RX_WINDOW_MAX_INFO, n_info == 0 when prev is NULL, d_info
+ * non-null when n_info > 0; ring_bytes, hold_off and hold_bytes >= 0 and hold_off + hold_bytes <=
+ * ring_bytes; base, first, len, dg of both windows, every d_info[j], d_pkt_first, d_pkt_len, d_pkt_dg and
+ * d_slot_group 4-byte aligned; off of both windows, d_pkt_off, d_summary and d_scratch 8-byte aligned; when
+ * groups > 0, non-null base, first and done of both windows, every d_info[j], d_pkt_first, d_slot_group,
+ * d_summary and d_scratch, non-null off, len and dg of a window unless its capacity is 0, non-null
+ * d_pkt_off, d_pkt_len and d_pkt_dg unless datagrams == 0, and non-null d_ring unless ring_bytes == 0; prev
+ * and next share no array. groups == 0 returns 0 and touches nothing.
+ *
+ * Asynchronous on `stream`, like the listing: four kernels, none of which waits on another workgroup; no
+ * host synchronisation, nothing is allocated after the stream's first call into the library, so the call
+ * can be captured into a graph (the pointers of prev, next and d_info are captured with it). Return codes:
+ * 0 ok, -1 invalid arguments, -2 GPU/runtime error.
+ */
+#define SHORTHAIR_RX_WINDOW_MAX_INFO 4       /* d_info arrays of the previous window's listing calls */
+#define SHORTHAIR_RX_HOLD_ALIGN 16           /* carried records start at multiples of this from hold_off */
+#define SHORTHAIR_RX_WINDOW_SCAN_TILE 16     /* consecutive slots one lane of the window scan sums */
+#define SHORTHAIR_RX_WINDOW_SCAN_PASS 4096   /* slots the window scan takes per pass */
+
+typedef struct {
+    int *base;           /* [1] unwrapped group of slot 0 */
+    int *first;          /* [groups + 1] */
+    long long *off;      /* [capacity] bytes from d_ring */
+    int *len;            /* [capacity] */
+    int *dg;             /* [capacity] datagram index within this batch; -1: carried from an earlier one */
+    unsigned char *done; /* [groups] 0 open, 1 finished, 2 malformed, 3 emptied by overflow */
+    int capacity;
+} ShorthairRxWindow;
+
+/* Bytes of device scratch the call below needs. Host only. -1 on invalid arguments (groups < 0,
+ * capacity < 0). */
+long long shorthair_rx_window_scratch_bytes(int groups, int capacity);
+
+int shorthair_rx_window_batch(int groups, const ShorthairRxWindow *prev /* NULL: a fresh receiver */,
+                              int n_info, const int *const *d_info /* host array of n_info device pointers, each [groups][8] */,
+                              int datagrams, const int *d_pkt_first, const long long *d_pkt_off,
+                              const int *d_pkt_len, const int *d_pkt_dg, const int *d_slot_group,
+                              void *d_ring, long long ring_bytes, long long hold_off, long long hold_bytes,
+                              const ShorthairRxWindow *next, long long *d_summary /* [8] */, void *d_scratch,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ __all__ = ["lib", "Block", "CAUCHY_256_VERSION", "cauchy_256_init", "cauchy_256_
            "encode_batch_var", "decode_batch_out_var", "frame_batch", "unframe_batch", "unframe_scratch_bytes", "wire_emit_batch",
            "rx_list_batch", "rx_list_capacity", "rx_list_scratch_bytes",
            "rx_group_batch", "rx_group_scratch_bytes",
+           "rx_window_batch", "rx_window_scratch_bytes", "RxWindow", "RxWindowStruct",
+           "RX_WINDOW_MAX_INFO", "RX_HOLD_ALIGN", "RX_WINDOW_SCAN_TILE", "RX_WINDOW_SCAN_PASS",
            "tx_datagram_batch", "tx_datagram_scratch_bytes", "tx_datagram_capacity", "TxGroupDesc",
            "TX_TILE", "TX_TILE_PASS", "TX_MAX_BLOCK_BYTES", "TX_MAX_DATAGRAM_BYTES",
            "RX_GROUP_TILE", "RX_GROUP_TILE_PASS", "RX_GROUP_SLOT_TILE", "RX_GROUP_SLOT_PASS",
@@ -46,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "shorthair_groups_set_delivery", "shorthair_wire_emit_batch", "shorthair_groups_set_wire",
     "shorthair_rx_list_capacity", "shorthair_rx_list_scratch_bytes", "shorthair_rx_list_batch",
     "shorthair_rx_group_scratch_bytes", "shorthair_rx_group_batch",
+    "shorthair_rx_window_scratch_bytes", "shorthair_rx_window_batch",
     "shorthair_tx_datagram_scratch_bytes", "shorthair_tx_datagram_capacity", "shorthair_tx_datagram_batch",
 ]
 
@@ -63,6 +66,12 @@ RX_GROUP_TILE = 256
 RX_GROUP_TILE_PASS = 1024
 RX_GROUP_SLOT_TILE = 16
 RX_GROUP_SLOT_PASS = 4096
+# include/shorthair_rx.h: d_info arrays rx_window_batch takes, the alignment of carried records in the hold
+# region, slots per lane and per pass of its scan
+RX_WINDOW_MAX_INFO = 4
+RX_HOLD_ALIGN = 16
+RX_WINDOW_SCAN_TILE = 16
+RX_WINDOW_SCAN_PASS = 4096
 # include/shorthair_tx.h: datagrams per tile of tx_datagram_batch, tiles per pass of its tile scan, the largest
 # recovery block and the largest datagram
 TX_TILE = 256
@@ -129,6 +138,11 @@ lib.shorthair_rx_group_scratch_bytes.argtypes = [_c.c_int] * 2
 lib.shorthair_rx_group_scratch_bytes.restype = _c.c_longlong
 lib.shorthair_rx_group_batch.argtypes = [_c.c_int] * 3 + [_c.c_void_p] * 3 + [_c.c_longlong] + [_c.c_void_p] * 13
 lib.shorthair_rx_group_batch.restype = _c.c_int
+lib.shorthair_rx_window_scratch_bytes.argtypes = [_c.c_int] * 2
+lib.shorthair_rx_window_scratch_bytes.restype = _c.c_longlong
+lib.shorthair_rx_window_batch.argtypes = ([_c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int] + [_c.c_void_p] * 6 +
+                                          [_c.c_longlong] * 3 + [_c.c_void_p] * 4)
+lib.shorthair_rx_window_batch.restype = _c.c_int
 lib.shorthair_tx_datagram_scratch_bytes.argtypes = [_c.c_int]
 lib.shorthair_tx_datagram_scratch_bytes.restype = _c.c_longlong
 lib.shorthair_tx_datagram_capacity.argtypes = [_c.c_int] * 3
@@ -354,6 +368,70 @@ def rx_group_batch(datagrams, groups, back, dg_off, dg_len, ring, ring_bytes, st
                                                ptr(pkt_first), ptr(pkt_off), ptr(pkt_len), ptr(pkt_dg),
                                                ptr(slot_group), ptr(other), ptr(summary), ptr(scratch),
                                                _stream(stream)), "rx_group_batch")
+
+
+class RxWindowStruct(ctypes.Structure):
+    """ShorthairRxWindow (include/shorthair_rx.h): a host struct of device pointers and the capacity."""
+    _fields_ = [("base", ctypes.c_void_p), ("first", ctypes.c_void_p), ("off", ctypes.c_void_p),
+                ("len", ctypes.c_void_p), ("dg", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("capacity", ctypes.c_int)]
+
+
+class RxWindow:
+    """One of a receiver's two windows on cuda tensors: base int32 [1], first int32 [groups + 1], off int64,
+    len and dg int32 [capacity], done uint8 [groups]. first, off and len are rx_list_batch's pkt_first,
+    pkt_off and pkt_len with packets = capacity. The tensors are allocated here unless passed in."""
+
+    def __init__(self, groups, capacity, base=None, first=None, off=None, len=None, dg=None, done=None):
+        import torch
+
+        def make(t, n, dtype):
+            return torch.zeros(n, dtype=dtype, device="cuda") if t is None else t
+        self.groups, self.capacity = groups, capacity
+        self.base = make(base, 1, torch.int32)
+        self.first = make(first, groups + 1, torch.int32)
+        self.off = make(off, capacity, torch.int64)
+        self.len = make(len, capacity, torch.int32)
+        self.dg = make(dg, capacity, torch.int32)
+        self.done = make(done, groups, torch.uint8)
+
+    def struct(self):
+        return RxWindowStruct(*[int(t.data_ptr()) for t in (self.base, self.first, self.off, self.len, self.dg,
+                                                              self.done)], self.capacity)
+
+
+def rx_window_scratch_bytes(groups, capacity):
+    """Bytes of device scratch rx_window_batch needs for (groups, the larger of the two windows' capacities).
+    Host only; raises ValueError on invalid arguments."""
+    n = lib.shorthair_rx_window_scratch_bytes(groups, capacity)
+    if n < 0:
+        raise ValueError("rx_window_scratch_bytes: bad arguments")
+    return n
+
+
+def rx_window_batch(groups, prev, infos, datagrams, pkt_first, pkt_off, pkt_len, pkt_dg, slot_group, ring, ring_bytes,
+                    hold_off, hold_bytes, nxt, summary, scratch, stream=None):
+    """Carry open groups from one receive batch to the next on the GPU (include/shorthair_rx.h): prev (an
+    RxWindow, an RxWindowStruct or None for a fresh receiver) and infos (the info tensors of the rx_list_batch
+    calls that ran over prev, at most RX_WINDOW_MAX_INFO) give the groups that are done; the open ones' records
+    are carried into nxt in front of the new records of rx_group_batch's pkt_first, pkt_off, pkt_len, pkt_dg
+    and slot_group, and copied to ring + hold_off when hold_bytes > 0. summary int64 [8], scratch uint8
+    [rx_window_scratch_bytes(groups, capacity)] (8-byte aligned): cuda tensors, or integer device addresses."""
+    def ptr(t):
+        return t if t is None or isinstance(t, int) else int(t.data_ptr())
+
+    def win(w):
+        if w is None or isinstance(w, RxWindowStruct):
+            return w
+        return w.struct()
+    p, n = win(prev), win(nxt)
+    infos = list(infos or ())
+    arr = (ctypes.c_void_p * max(len(infos), 1))(*[ptr(t) for t in infos])
+    return _check(lib.shorthair_rx_window_batch(groups, None if p is None else ctypes.addressof(p), len(infos),
+                                                ctypes.addressof(arr), datagrams, ptr(pkt_first), ptr(pkt_off),
+                                                ptr(pkt_len), ptr(pkt_dg), ptr(slot_group), ptr(ring), ring_bytes,
+                                                hold_off, hold_bytes, None if n is None else ctypes.addressof(n),
+                                                ptr(summary), ptr(scratch), _stream(stream)), "rx_window_batch")
 
 
 class TxGroupDesc(ctypes.Structure):

@@ -34,6 +34,7 @@
 #include "measure.hpp"
 #include "rx_group.hpp"
 #include "rx_list.hpp"
+#include "rx_window.hpp"
 #include "stagea_route.hpp"
 #include "tx_datagram.hpp"
 #include "unframe.hpp"
@@ -1137,6 +1138,89 @@ extern "C" int shorthair_rx_group_batch(int datagrams, int groups, int back, con
     // under the stream's lock, like the listing's count
     std::lock_guard<std::mutex> g(st->mu);
     SH_CHECK(sh::launch_rx_group(a, d_scratch, s));
+    return 0;
+}
+
+extern "C" long long shorthair_rx_window_scratch_bytes(int groups, int capacity) {
+    if (groups < 0 || capacity < 0) return -1;
+    return sh::rx_window_scratch_bytes(groups, capacity);
+}
+
+extern "C" int shorthair_rx_window_batch(int groups, const ShorthairRxWindow *prev, int n_info,
+                                         const int *const *d_info, int datagrams, const int *d_pkt_first,
+                                         const long long *d_pkt_off, const int *d_pkt_len, const int *d_pkt_dg,
+                                         const int *d_slot_group, void *d_ring, long long ring_bytes,
+                                         long long hold_off, long long hold_bytes, const ShorthairRxWindow *next,
+                                         long long *d_summary, void *d_scratch, void *stream) {
+    if (groups < 0 || datagrams < 0 || !next || next->capacity < 0 || (prev && prev->capacity < 0)) return -1;
+    if (n_info < 0 || n_info > SHORTHAIR_RX_WINDOW_MAX_INFO || (!prev && n_info != 0) || (n_info > 0 && !d_info)) return -1;
+    if (ring_bytes < 0 || hold_off < 0 || hold_bytes < 0 || hold_off > ring_bytes - hold_bytes) return -1;
+    auto mis = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
+    for (const ShorthairRxWindow *w : {prev, next}) {
+        if (!w) continue;
+        if (mis(w->base, 4) || mis(w->first, 4) || mis(w->len, 4) || mis(w->dg, 4) || mis(w->off, 8)) return -1;
+        if (groups > 0 && (!w->base || !w->first || !w->done)) return -1;
+        if (groups > 0 && w->capacity > 0 && (!w->off || !w->len || !w->dg)) return -1;
+    }
+    for (int q = 0; q < n_info; ++q)
+        if (mis(d_info[q], 4) || (groups > 0 && !d_info[q])) return -1;
+    if (mis(d_pkt_first, 4) || mis(d_pkt_len, 4) || mis(d_pkt_dg, 4) || mis(d_slot_group, 4) || mis(d_pkt_off, 8) ||
+        mis(d_summary, 8) || mis(d_scratch, 8))
+        return -1;
+    if (groups > 0) {
+        if (!d_pkt_first || !d_slot_group || !d_summary || !d_scratch) return -1;
+        if (datagrams > 0 && (!d_pkt_off || !d_pkt_len || !d_pkt_dg)) return -1;
+        if (ring_bytes > 0 && !d_ring) return -1;
+    }
+    if (prev) {  // the two windows share no array
+        const void *a[6] = {prev->base, prev->first, prev->off, prev->len, prev->dg, prev->done};
+        const void *b[6] = {next->base, next->first, next->off, next->len, next->dg, next->done};
+        for (const void *x : a)
+            for (const void *y : b)
+                if (x && x == y) return -1;
+    }
+    if (groups == 0) return 0;
+    Context &c = ctx();
+    DeviceScope ds(c);
+    if (ds.rc) return ds.rc;
+    hipStream_t s = pick(stream);
+    StreamState *st = stream_state(c, s);
+    if (!st) return -2;
+    sh::RxWindowArgs a{};
+    a.has_prev = prev != nullptr;
+    if (prev) {
+        a.p_base = prev->base;
+        a.p_first = prev->first;
+        a.p_off = prev->off;
+        a.p_len = prev->len;
+        a.p_done = prev->done;
+        a.p_cap = prev->capacity;
+    }
+    a.n_info = n_info;
+    for (int q = 0; q < n_info; ++q) a.info[q] = d_info[q];
+    a.g_first = d_pkt_first;
+    a.g_off = d_pkt_off;
+    a.g_len = d_pkt_len;
+    a.g_dg = d_pkt_dg;
+    a.g_slot_group = d_slot_group;
+    a.ring = static_cast<uint8_t *>(d_ring);
+    a.ring_bytes = ring_bytes;
+    a.hold_off = hold_off;
+    a.hold_bytes = hold_bytes;
+    a.n_base = next->base;
+    a.n_first = next->first;
+    a.n_off = next->off;
+    a.n_len = next->len;
+    a.n_dg = next->dg;
+    a.n_done = next->done;
+    a.n_cap = next->capacity;
+    a.summary = d_summary;
+    a.errors = st->d_errors;
+    a.groups = groups;
+    a.datagrams = datagrams;
+    // under the stream's lock, like the listing's count
+    std::lock_guard<std::mutex> g(st->mu);
+    SH_CHECK(sh::launch_rx_window(a, d_scratch, s));
     return 0;
 }
 

@@ -212,6 +212,18 @@ def _ptr(t):
     return None if t is None else int(t.data_ptr())
 
 
+def _addr(t):
+    """The packet calls' pointer convention: a cuda tensor, an integer device address or None."""
+    return t if t is None or isinstance(t, int) else int(t.data_ptr())
+
+
+def _size(n, what):
+    """The result of a host-only size query: the library answers -1 for bad arguments."""
+    if n < 0:
+        raise ValueError(f"{what}: bad arguments")
+    return n
+
+
 def _stream(stream):
     if stream is None:
         import torch
@@ -262,19 +274,14 @@ def frame_batch(block_bytes, total_blocks, payload, payload_bytes, off, length, 
     off[j] verbatim where raw[j] != 0. payload uint8, off int64 [total_blocks], length int32
     [total_blocks], raw uint8 [total_blocks] or None, blocks uint8 (8-byte aligned): cuda tensors, or
     integer device addresses."""
-    def ptr(t):
-        return t if t is None or isinstance(t, int) else int(t.data_ptr())
-    return _check(lib.shorthair_frame_batch(block_bytes, total_blocks, ptr(payload), payload_bytes, ptr(off),
-                                            ptr(length), ptr(raw), ptr(blocks), _stream(stream)), "frame_batch")
+    return _check(lib.shorthair_frame_batch(block_bytes, total_blocks, _addr(payload), payload_bytes, _addr(off),
+                                            _addr(length), _addr(raw), _addr(blocks), _stream(stream)), "frame_batch")
 
 
 def unframe_scratch_bytes(groups, emax):
     """Bytes of device scratch unframe_batch needs for (groups, emax). Host only; raises ValueError on
     invalid arguments."""
-    n = lib.shorthair_unframe_scratch_bytes(groups, emax)
-    if n < 0:
-        raise ValueError("unframe_scratch_bytes: bad arguments")
-    return n
+    return _size(lib.shorthair_unframe_scratch_bytes(groups, emax), "unframe_scratch_bytes")
 
 
 def unframe_batch(block_bytes, groups, emax, group_stride_blocks, out, out_count, payload, payload_capacity,
@@ -286,11 +293,9 @@ def unframe_batch(block_bytes, groups, emax, group_stride_blocks, out, out_count
     [groups] or None, payload uint8 [payload_capacity], off int64 [groups * emax + 1], length int32
     [groups * emax], scratch uint8 [unframe_scratch_bytes(groups, emax)]: cuda tensors, or integer device
     addresses."""
-    def ptr(t):
-        return t if t is None or isinstance(t, int) else int(t.data_ptr())
-    return _check(lib.shorthair_unframe_batch(block_bytes, groups, emax, group_stride_blocks, ptr(out),
-                                              ptr(out_count), ptr(payload), payload_capacity, ptr(off),
-                                              ptr(length), ptr(scratch), _stream(stream)), "unframe_batch")
+    return _check(lib.shorthair_unframe_batch(block_bytes, groups, emax, group_stride_blocks, _addr(out),
+                                              _addr(out_count), _addr(payload), payload_capacity, _addr(off),
+                                              _addr(length), _addr(scratch), _stream(stream)), "unframe_batch")
 
 
 def wire_emit_batch(k, m, block_bytes, groups, first, total_blocks, recovery, wire, stream=None):
@@ -299,28 +304,20 @@ def wire_emit_batch(k, m, block_bytes, groups, first, total_blocks, recovery, wi
     first[g] with first int32 [groups + 1] (k is then kmax; a malformed group's records are zeros).
     recovery uint8 [groups][m][B] (8-byte aligned), wire uint8 at any address: cuda tensors, or integer
     device addresses; first a tensor, an address or None."""
-    def ptr(t):
-        return t if t is None or isinstance(t, int) else int(t.data_ptr())
-    return _check(lib.shorthair_wire_emit_batch(k, m, block_bytes, groups, ptr(first), total_blocks, ptr(recovery),
-                                                ptr(wire), _stream(stream)), "wire_emit_batch")
+    return _check(lib.shorthair_wire_emit_batch(k, m, block_bytes, groups, _addr(first), total_blocks, _addr(recovery),
+                                                _addr(wire), _stream(stream)), "wire_emit_batch")
 
 
 def rx_list_capacity(groups, packets, kmax):
     """Entries of each list array of rx_list_batch: min(packets, groups * kmax). Host only; raises
     ValueError on invalid arguments."""
-    n = lib.shorthair_rx_list_capacity(groups, packets, kmax)
-    if n < 0:
-        raise ValueError("rx_list_capacity: bad arguments")
-    return n
+    return _size(lib.shorthair_rx_list_capacity(groups, packets, kmax), "rx_list_capacity")
 
 
 def rx_list_scratch_bytes(groups, packets):
     """Bytes of device scratch rx_list_batch needs for (groups, packets). Host only; raises ValueError
     on invalid arguments."""
-    n = lib.shorthair_rx_list_scratch_bytes(groups, packets)
-    if n < 0:
-        raise ValueError("rx_list_scratch_bytes: bad arguments")
-    return n
+    return _size(lib.shorthair_rx_list_scratch_bytes(groups, packets), "rx_list_scratch_bytes")
 
 
 def rx_list_batch(kmin, kmax, m, block_bytes, groups, packets, pkt_first, pkt_off, pkt_len, ring, ring_bytes,
@@ -333,22 +330,17 @@ def rx_list_batch(kmin, kmax, m, block_bytes, groups, packets, pkt_first, pkt_of
     int32 [groups + 1], pkt_off int64 [packets], pkt_len int32 [packets], ring uint8 [ring_bytes], scratch
     uint8 [rx_list_scratch_bytes(groups, packets)] (8-byte aligned): cuda tensors, or integer device
     addresses."""
-    def ptr(t):
-        return t if t is None or isinstance(t, int) else int(t.data_ptr())
-    return _check(lib.shorthair_rx_list_batch(kmin, kmax, m, block_bytes, groups, packets, ptr(pkt_first),
-                                              ptr(pkt_off), ptr(pkt_len), ptr(ring), ring_bytes, ptr(info),
-                                              ptr(first), ptr(slot_group), ptr(off), ptr(length), ptr(raw),
-                                              ptr(rows), ptr(summary), ptr(scratch), _stream(stream)),
+    return _check(lib.shorthair_rx_list_batch(kmin, kmax, m, block_bytes, groups, packets, _addr(pkt_first),
+                                              _addr(pkt_off), _addr(pkt_len), _addr(ring), ring_bytes, _addr(info),
+                                              _addr(first), _addr(slot_group), _addr(off), _addr(length), _addr(raw),
+                                              _addr(rows), _addr(summary), _addr(scratch), _stream(stream)),
                   "rx_list_batch")
 
 
 def rx_group_scratch_bytes(datagrams, groups):
     """Bytes of device scratch rx_group_batch needs for (datagrams, groups). Host only; raises ValueError
     on invalid arguments."""
-    n = lib.shorthair_rx_group_scratch_bytes(datagrams, groups)
-    if n < 0:
-        raise ValueError("rx_group_scratch_bytes: bad arguments")
-    return n
+    return _size(lib.shorthair_rx_group_scratch_bytes(datagrams, groups), "rx_group_scratch_bytes")
 
 
 def rx_group_batch(datagrams, groups, back, dg_off, dg_len, ring, ring_bytes, state_in, state_out, dg_class, dg_slot,
@@ -361,12 +353,10 @@ def rx_group_batch(datagrams, groups, back, dg_off, dg_len, ring, ring_bytes, st
     summary int32 [8]. dg_off int64 [datagrams], dg_len int32 [datagrams], ring uint8 [ring_bytes], scratch
     uint8 [rx_group_scratch_bytes(datagrams, groups)] (8-byte aligned): cuda tensors, or integer device
     addresses."""
-    def ptr(t):
-        return t if t is None or isinstance(t, int) else int(t.data_ptr())
-    return _check(lib.shorthair_rx_group_batch(datagrams, groups, back, ptr(dg_off), ptr(dg_len), ptr(ring), ring_bytes,
-                                               ptr(state_in), ptr(state_out), ptr(dg_class), ptr(dg_slot),
-                                               ptr(pkt_first), ptr(pkt_off), ptr(pkt_len), ptr(pkt_dg),
-                                               ptr(slot_group), ptr(other), ptr(summary), ptr(scratch),
+    return _check(lib.shorthair_rx_group_batch(datagrams, groups, back, _addr(dg_off), _addr(dg_len), _addr(ring), ring_bytes,
+                                               _addr(state_in), _addr(state_out), _addr(dg_class), _addr(dg_slot),
+                                               _addr(pkt_first), _addr(pkt_off), _addr(pkt_len), _addr(pkt_dg),
+                                               _addr(slot_group), _addr(other), _addr(summary), _addr(scratch),
                                                _stream(stream)), "rx_group_batch")
 
 
@@ -403,10 +393,7 @@ class RxWindow:
 def rx_window_scratch_bytes(groups, capacity):
     """Bytes of device scratch rx_window_batch needs for (groups, the larger of the two windows' capacities).
     Host only; raises ValueError on invalid arguments."""
-    n = lib.shorthair_rx_window_scratch_bytes(groups, capacity)
-    if n < 0:
-        raise ValueError("rx_window_scratch_bytes: bad arguments")
-    return n
+    return _size(lib.shorthair_rx_window_scratch_bytes(groups, capacity), "rx_window_scratch_bytes")
 
 
 def rx_window_batch(groups, prev, infos, datagrams, pkt_first, pkt_off, pkt_len, pkt_dg, slot_group, ring, ring_bytes,
@@ -417,21 +404,18 @@ def rx_window_batch(groups, prev, infos, datagrams, pkt_first, pkt_off, pkt_len,
     are carried into nxt in front of the new records of rx_group_batch's pkt_first, pkt_off, pkt_len, pkt_dg
     and slot_group, and copied to ring + hold_off when hold_bytes > 0. summary int64 [8], scratch uint8
     [rx_window_scratch_bytes(groups, capacity)] (8-byte aligned): cuda tensors, or integer device addresses."""
-    def ptr(t):
-        return t if t is None or isinstance(t, int) else int(t.data_ptr())
-
     def win(w):
         if w is None or isinstance(w, RxWindowStruct):
             return w
         return w.struct()
     p, n = win(prev), win(nxt)
     infos = list(infos or ())
-    arr = (ctypes.c_void_p * max(len(infos), 1))(*[ptr(t) for t in infos])
+    arr = (ctypes.c_void_p * max(len(infos), 1))(*[_addr(t) for t in infos])
     return _check(lib.shorthair_rx_window_batch(groups, None if p is None else ctypes.addressof(p), len(infos),
-                                                ctypes.addressof(arr), datagrams, ptr(pkt_first), ptr(pkt_off),
-                                                ptr(pkt_len), ptr(pkt_dg), ptr(slot_group), ptr(ring), ring_bytes,
+                                                ctypes.addressof(arr), datagrams, _addr(pkt_first), _addr(pkt_off),
+                                                _addr(pkt_len), _addr(pkt_dg), _addr(slot_group), _addr(ring), ring_bytes,
                                                 hold_off, hold_bytes, None if n is None else ctypes.addressof(n),
-                                                ptr(summary), ptr(scratch), _stream(stream)), "rx_window_batch")
+                                                _addr(summary), _addr(scratch), _stream(stream)), "rx_window_batch")
 
 
 class TxGroupDesc(ctypes.Structure):
@@ -442,19 +426,13 @@ class TxGroupDesc(ctypes.Structure):
 
 def tx_datagram_scratch_bytes(datagrams):
     """Bytes of device scratch tx_datagram_batch needs. Host only; raises ValueError on invalid arguments."""
-    n = lib.shorthair_tx_datagram_scratch_bytes(datagrams)
-    if n < 0:
-        raise ValueError("tx_datagram_scratch_bytes: bad arguments")
-    return n
+    return _size(lib.shorthair_tx_datagram_scratch_bytes(datagrams), "tx_datagram_scratch_bytes")
 
 
 def tx_datagram_capacity(datagrams, max_datagram_bytes, align):
     """Ring bytes that always suffice for `datagrams` datagrams of at most max_datagram_bytes placed at
     multiples of align. Host only; raises ValueError on invalid arguments."""
-    n = lib.shorthair_tx_datagram_capacity(datagrams, max_datagram_bytes, align)
-    if n < 0:
-        raise ValueError("tx_datagram_capacity: bad arguments")
-    return n
+    return _size(lib.shorthair_tx_datagram_capacity(datagrams, max_datagram_bytes, align), "tx_datagram_capacity")
 
 
 def tx_datagram_batch(datagrams, groups, m, block_bytes, sched, first, total_blocks, payload, payload_bytes, off,
@@ -469,14 +447,12 @@ def tx_datagram_batch(datagrams, groups, m, block_bytes, sched, first, total_blo
     state_in and state_out int32 [2] (may be the same), ring uint8 [ring_bytes], dg_off int64 [datagrams + 1],
     dg_len and dg_class int32 [datagrams], summary int32 [8], scratch uint8
     [tx_datagram_scratch_bytes(datagrams)] (8-byte aligned): cuda tensors, or integer device addresses."""
-    def ptr(t):
-        return t if t is None or isinstance(t, int) else int(t.data_ptr())
-    return _check(lib.shorthair_tx_datagram_batch(datagrams, groups, m, block_bytes, ptr(sched), ptr(first),
-                                                  total_blocks, ptr(payload), payload_bytes, ptr(off), ptr(length),
-                                                  ptr(recovery), recovery_bytes, ptr(group), n_pong, ptr(pong_at),
-                                                  ptr(pong_val), advance, ptr(state_in), ptr(state_out), align,
-                                                  ptr(ring), ring_bytes, ptr(dg_off), ptr(dg_len), ptr(dg_class),
-                                                  ptr(summary), ptr(scratch), _stream(stream)),
+    return _check(lib.shorthair_tx_datagram_batch(datagrams, groups, m, block_bytes, _addr(sched), _addr(first),
+                                                  total_blocks, _addr(payload), payload_bytes, _addr(off), _addr(length),
+                                                  _addr(recovery), recovery_bytes, _addr(group), n_pong, _addr(pong_at),
+                                                  _addr(pong_val), advance, _addr(state_in), _addr(state_out), align,
+                                                  _addr(ring), ring_bytes, _addr(dg_off), _addr(dg_len), _addr(dg_class),
+                                                  _addr(summary), _addr(scratch), _stream(stream)),
                   "tx_datagram_batch")
 
 

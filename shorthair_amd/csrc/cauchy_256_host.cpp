@@ -22,23 +22,12 @@
 
 #include "../../include/cauchy_256.h"
 #include "../../include/cauchy_256_batch.h"
-#include "../../include/shorthair_frame.h"
-#include "../../include/shorthair_rx.h"
-#include "../../include/shorthair_tx.h"
-#include "../../include/shorthair_unframe.h"
-#include "../../include/shorthair_wire.h"
 #include "cauchy_math.hpp"
 #include "colsnip.h"
-#include "frame.hpp"
 #include "kernels.hpp"
 #include "measure.hpp"
-#include "rx_group.hpp"
-#include "rx_list.hpp"
-#include "rx_window.hpp"
 #include "stagea_route.hpp"
-#include "tx_datagram.hpp"
-#include "unframe.hpp"
-#include "wire.hpp"
+#include "stream_call.hpp"
 
 namespace {
 
@@ -900,6 +889,29 @@ int decode_batch(int k, int m, int B, int groups, uint8_t *d_blocks, uint8_t *d_
 
 }  // namespace
 
+// csrc/stream_call.hpp. (Held's members leave in reverse order: the lock first, then the device.)
+struct sh::StreamCall::Held {
+    DeviceScope ds;
+    std::unique_lock<std::mutex> lk;
+    explicit Held(Context &c) : ds(c) {}
+};
+
+sh::StreamCall::StreamCall(void *stream_, bool counts) : stream(pick(stream_)) {
+    Context &c = ctx();
+    held_ = std::make_unique<Held>(c);
+    rc = held_->ds.rc;
+    if (rc || !counts) return;
+    StreamState *st = stream_state(c, stream);
+    if (!st) {
+        rc = -2;
+        return;
+    }
+    held_->lk = std::unique_lock<std::mutex>(st->mu);
+    errors = st->d_errors;
+}
+
+sh::StreamCall::~StreamCall() = default;
+
 // =============================================================================================
 // Batched device ABI (cauchy_256_batch.h)
 // =============================================================================================
@@ -983,355 +995,6 @@ extern "C" int cauchy_256_decode_batch_out_var(int kmax, int m, int block_bytes,
                             pick(stream));
 }
 
-extern "C" int shorthair_frame_batch(int block_bytes, int total_blocks, const void *d_payload,
-                                     long long payload_bytes, const long long *d_off, const int *d_len,
-                                     const unsigned char *d_raw, void *d_blocks, void *stream) {
-    if (block_bytes < 8 || block_bytes % 8 != 0 || total_blocks < 0 || payload_bytes < 0) return -1;
-    if (total_blocks > 0 && (!d_payload || !d_off || !d_len || !d_blocks)) return -1;
-    if (reinterpret_cast<uintptr_t>(d_blocks) % 8 != 0) return -1;
-    if (total_blocks == 0) return 0;
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    hipStream_t s = pick(stream);
-    StreamState *st = stream_state(c, s);
-    if (!st) return -2;
-    // under the stream's lock, like the var-k encode's count (encode_batch)
-    std::lock_guard<std::mutex> g(st->mu);
-    SH_CHECK(sh::launch_frame(block_bytes, total_blocks, static_cast<const uint8_t *>(d_payload), payload_bytes,
-                              d_off, d_len, d_raw, static_cast<uint8_t *>(d_blocks), st->d_errors, s));
-    return 0;
-}
-
-extern "C" int shorthair_wire_emit_batch(int k, int m, int block_bytes, int groups, const int *d_first,
-                                         int total_blocks, const void *d_recovery, void *d_wire, void *stream) {
-    if (k < 2 || k > 255 || m < 1 || k + m > 256 || block_bytes < 8 || block_bytes % 8 != 0 || groups < 0) return -1;
-    if (static_cast<long long>(groups) * m > 0x7fffffffll) return -1;
-    if (d_first && (total_blocks < 0 || static_cast<long long>(total_blocks) > static_cast<long long>(groups) * k ||
-                    reinterpret_cast<uintptr_t>(d_first) % 4 != 0))
-        return -1;
-    if (groups > 0 && (!d_recovery || !d_wire)) return -1;
-    if (reinterpret_cast<uintptr_t>(d_recovery) % 8 != 0) return -1;
-    if (groups == 0) return 0;
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    // (no stream state: the call counts nothing and needs no workspace)
-    SH_CHECK(sh::launch_wire_emit(k, m, block_bytes, groups, d_first, total_blocks,
-                                  static_cast<const uint8_t *>(d_recovery), static_cast<uint8_t *>(d_wire),
-                                  pick(stream)));
-    return 0;
-}
-
-extern "C" int shorthair_rx_list_capacity(int groups, int packets, int kmax) {
-    if (groups < 0 || packets < 0 || kmax < 2 || kmax > 255) return -1;
-    return static_cast<int>(std::min<long long>(packets, static_cast<long long>(groups) * kmax));
-}
-
-extern "C" long long shorthair_rx_list_scratch_bytes(int groups, int packets) {
-    if (groups < 0 || packets < 0) return -1;
-    return sh::rx_list_scratch_bytes(groups, packets);
-}
-
-extern "C" int shorthair_rx_list_batch(int kmin, int kmax, int m, int block_bytes, int groups, int packets,
-                                       const int *d_pkt_first, const long long *d_pkt_off, const int *d_pkt_len,
-                                       const void *d_ring, long long ring_bytes, int *d_info, int *d_first,
-                                       int *d_slot_group, long long *d_off, int *d_len, unsigned char *d_raw,
-                                       unsigned char *d_rows, int *d_summary, void *d_scratch, void *stream) {
-    if (kmin < 2 || kmin > kmax || kmax > 255 || m < 1 || kmax + m > 256) return -1;
-    if (block_bytes < 8 || block_bytes % 8 != 0 || groups < 0 || packets < 0 || ring_bytes < 0) return -1;
-    auto mis = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
-    if (mis(d_pkt_first, 4) || mis(d_pkt_len, 4) || mis(d_info, 4) || mis(d_first, 4) || mis(d_slot_group, 4) ||
-        mis(d_len, 4) || mis(d_summary, 4) || mis(d_pkt_off, 8) || mis(d_off, 8) || mis(d_scratch, 8))
-        return -1;
-    const int capacity = shorthair_rx_list_capacity(groups, packets, kmax);
-    if (groups > 0) {
-        if (!d_pkt_first || !d_info || !d_first || !d_slot_group || !d_summary || !d_scratch) return -1;
-        if (packets > 0 && (!d_pkt_off || !d_pkt_len || !d_ring)) return -1;
-        if (capacity > 0 && (!d_off || !d_len || !d_raw || !d_rows)) return -1;
-    }
-    if (groups == 0) return 0;
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    hipStream_t s = pick(stream);
-    StreamState *st = stream_state(c, s);
-    if (!st) return -2;
-    sh::RxListArgs a{};
-    a.pkt_first = d_pkt_first;
-    a.pkt_off = d_pkt_off;
-    a.pkt_len = d_pkt_len;
-    a.ring = static_cast<const uint8_t *>(d_ring);
-    a.ring_bytes = ring_bytes;
-    a.info = d_info;
-    a.first = d_first;
-    a.slot_group = d_slot_group;
-    a.off = d_off;
-    a.len = d_len;
-    a.raw = d_raw;
-    a.rows = d_rows;
-    a.summary = d_summary;
-    a.errors = st->d_errors;
-    a.kmin = kmin;
-    a.kmax = kmax;
-    a.m = m;
-    a.B = block_bytes;
-    a.groups = groups;
-    a.packets = packets;
-    a.capacity = capacity;
-    // under the stream's lock, like shorthair_frame_batch's count
-    std::lock_guard<std::mutex> g(st->mu);
-    SH_CHECK(sh::launch_rx_list(a, d_scratch, s));
-    return 0;
-}
-
-extern "C" long long shorthair_rx_group_scratch_bytes(int datagrams, int groups) {
-    if (datagrams < 0 || groups < 0) return -1;
-    return sh::rx_group_scratch_bytes(datagrams, groups);
-}
-
-extern "C" int shorthair_rx_group_batch(int datagrams, int groups, int back, const long long *d_dg_off,
-                                        const int *d_dg_len, const void *d_ring, long long ring_bytes,
-                                        const int *d_state_in, int *d_state_out, int *d_dg_class, int *d_dg_slot,
-                                        int *d_pkt_first, long long *d_pkt_off, int *d_pkt_len, int *d_pkt_dg,
-                                        int *d_slot_group, int *d_other, int *d_summary, void *d_scratch,
-                                        void *stream) {
-    if (datagrams < 0 || groups < 0 || back < 0 || back > groups || ring_bytes < 0) return -1;
-    auto mis = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
-    if (mis(d_dg_len, 4) || mis(d_state_in, 4) || mis(d_state_out, 4) || mis(d_dg_class, 4) || mis(d_dg_slot, 4) ||
-        mis(d_pkt_first, 4) || mis(d_pkt_len, 4) || mis(d_pkt_dg, 4) || mis(d_slot_group, 4) || mis(d_other, 4) ||
-        mis(d_summary, 4) || mis(d_dg_off, 8) || mis(d_pkt_off, 8) || mis(d_scratch, 8))
-        return -1;
-    if (groups > 0) {
-        if (!d_state_in || !d_state_out || !d_pkt_first || !d_slot_group || !d_summary || !d_scratch) return -1;
-        if (datagrams > 0 && (!d_dg_off || !d_dg_len || !d_ring || !d_dg_class || !d_dg_slot || !d_pkt_off ||
-                              !d_pkt_len || !d_pkt_dg || !d_other))
-            return -1;
-    }
-    if (groups == 0) return 0;
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    hipStream_t s = pick(stream);
-    StreamState *st = stream_state(c, s);
-    if (!st) return -2;
-    sh::RxGroupArgs a{};
-    a.dg_off = d_dg_off;
-    a.dg_len = d_dg_len;
-    a.ring = static_cast<const uint8_t *>(d_ring);
-    a.ring_bytes = ring_bytes;
-    a.state_in = d_state_in;
-    a.state_out = d_state_out;
-    a.dg_class = d_dg_class;
-    a.dg_slot = d_dg_slot;
-    a.pkt_first = d_pkt_first;
-    a.pkt_off = d_pkt_off;
-    a.pkt_len = d_pkt_len;
-    a.pkt_dg = d_pkt_dg;
-    a.slot_group = d_slot_group;
-    a.other = d_other;
-    a.summary = d_summary;
-    a.errors = st->d_errors;
-    a.datagrams = datagrams;
-    a.groups = groups;
-    a.back = back;
-    // under the stream's lock, like the listing's count
-    std::lock_guard<std::mutex> g(st->mu);
-    SH_CHECK(sh::launch_rx_group(a, d_scratch, s));
-    return 0;
-}
-
-extern "C" long long shorthair_rx_window_scratch_bytes(int groups, int capacity) {
-    if (groups < 0 || capacity < 0) return -1;
-    return sh::rx_window_scratch_bytes(groups, capacity);
-}
-
-extern "C" int shorthair_rx_window_batch(int groups, const ShorthairRxWindow *prev, int n_info,
-                                         const int *const *d_info, int datagrams, const int *d_pkt_first,
-                                         const long long *d_pkt_off, const int *d_pkt_len, const int *d_pkt_dg,
-                                         const int *d_slot_group, void *d_ring, long long ring_bytes,
-                                         long long hold_off, long long hold_bytes, const ShorthairRxWindow *next,
-                                         long long *d_summary, void *d_scratch, void *stream) {
-    if (groups < 0 || datagrams < 0 || !next || next->capacity < 0 || (prev && prev->capacity < 0)) return -1;
-    if (n_info < 0 || n_info > SHORTHAIR_RX_WINDOW_MAX_INFO || (!prev && n_info != 0) || (n_info > 0 && !d_info)) return -1;
-    if (ring_bytes < 0 || hold_off < 0 || hold_bytes < 0 || hold_off > ring_bytes - hold_bytes) return -1;
-    auto mis = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
-    for (const ShorthairRxWindow *w : {prev, next}) {
-        if (!w) continue;
-        if (mis(w->base, 4) || mis(w->first, 4) || mis(w->len, 4) || mis(w->dg, 4) || mis(w->off, 8)) return -1;
-        if (groups > 0 && (!w->base || !w->first || !w->done)) return -1;
-        if (groups > 0 && w->capacity > 0 && (!w->off || !w->len || !w->dg)) return -1;
-    }
-    for (int q = 0; q < n_info; ++q)
-        if (mis(d_info[q], 4) || (groups > 0 && !d_info[q])) return -1;
-    if (mis(d_pkt_first, 4) || mis(d_pkt_len, 4) || mis(d_pkt_dg, 4) || mis(d_slot_group, 4) || mis(d_pkt_off, 8) ||
-        mis(d_summary, 8) || mis(d_scratch, 8))
-        return -1;
-    if (groups > 0) {
-        if (!d_pkt_first || !d_slot_group || !d_summary || !d_scratch) return -1;
-        if (datagrams > 0 && (!d_pkt_off || !d_pkt_len || !d_pkt_dg)) return -1;
-        if (ring_bytes > 0 && !d_ring) return -1;
-    }
-    if (prev) {  // the two windows share no array
-        const void *a[6] = {prev->base, prev->first, prev->off, prev->len, prev->dg, prev->done};
-        const void *b[6] = {next->base, next->first, next->off, next->len, next->dg, next->done};
-        for (const void *x : a)
-            for (const void *y : b)
-                if (x && x == y) return -1;
-    }
-    if (groups == 0) return 0;
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    hipStream_t s = pick(stream);
-    StreamState *st = stream_state(c, s);
-    if (!st) return -2;
-    sh::RxWindowArgs a{};
-    a.has_prev = prev != nullptr;
-    if (prev) {
-        a.p_base = prev->base;
-        a.p_first = prev->first;
-        a.p_off = prev->off;
-        a.p_len = prev->len;
-        a.p_done = prev->done;
-        a.p_cap = prev->capacity;
-    }
-    a.n_info = n_info;
-    for (int q = 0; q < n_info; ++q) a.info[q] = d_info[q];
-    a.g_first = d_pkt_first;
-    a.g_off = d_pkt_off;
-    a.g_len = d_pkt_len;
-    a.g_dg = d_pkt_dg;
-    a.g_slot_group = d_slot_group;
-    a.ring = static_cast<uint8_t *>(d_ring);
-    a.ring_bytes = ring_bytes;
-    a.hold_off = hold_off;
-    a.hold_bytes = hold_bytes;
-    a.n_base = next->base;
-    a.n_first = next->first;
-    a.n_off = next->off;
-    a.n_len = next->len;
-    a.n_dg = next->dg;
-    a.n_done = next->done;
-    a.n_cap = next->capacity;
-    a.summary = d_summary;
-    a.errors = st->d_errors;
-    a.groups = groups;
-    a.datagrams = datagrams;
-    // under the stream's lock, like the listing's count
-    std::lock_guard<std::mutex> g(st->mu);
-    SH_CHECK(sh::launch_rx_window(a, d_scratch, s));
-    return 0;
-}
-
-extern "C" long long shorthair_tx_datagram_scratch_bytes(int datagrams) {
-    if (datagrams < 0) return -1;
-    return sh::tx_datagram_scratch_bytes(datagrams);
-}
-
-extern "C" long long shorthair_tx_datagram_capacity(int datagrams, int max_datagram_bytes, int align) {
-    if (datagrams < 0 || max_datagram_bytes < 0 || align < 1 || align > 4096 || (align & (align - 1))) return -1;
-    const long long each = (static_cast<long long>(max_datagram_bytes) + align - 1) & ~static_cast<long long>(align - 1);
-    return datagrams * each;
-}
-
-extern "C" int shorthair_tx_datagram_batch(int datagrams, int groups, int m, int block_bytes, const int *d_sched,
-                                           const int *d_first, int total_blocks, const void *d_payload,
-                                           long long payload_bytes, const long long *d_off, const int *d_len,
-                                           const void *d_recovery, long long recovery_bytes,
-                                           const ShorthairTxGroupDesc *d_group, int n_pong, const int *d_pong_at,
-                                           const unsigned *d_pong_val, int advance, const int *d_state_in,
-                                           int *d_state_out, int align, void *d_ring, long long ring_bytes,
-                                           long long *d_dg_off, int *d_dg_len, int *d_dg_class, int *d_summary,
-                                           void *d_scratch, void *stream) {
-    if (datagrams < 0 || groups < 0 || groups > (1 << 22) || m < 0 || block_bytes < 0 || total_blocks < 0) return -1;
-    if (payload_bytes < 0 || recovery_bytes < 0 || ring_bytes < 0 || n_pong < 0 || advance < 0) return -1;
-    if (align < 1 || align > 4096 || (align & (align - 1))) return -1;
-    auto mis = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
-    if (mis(d_sched, 4) || mis(d_first, 4) || mis(d_len, 4) || mis(d_pong_at, 4) || mis(d_pong_val, 4) ||
-        mis(d_state_in, 4) || mis(d_state_out, 4) || mis(d_dg_len, 4) || mis(d_dg_class, 4) || mis(d_summary, 4) ||
-        mis(d_off, 8) || mis(d_group, 8) || mis(d_recovery, 8) || mis(d_dg_off, 8) || mis(d_scratch, 8))
-        return -1;
-    if (!d_state_in || !d_state_out || !d_dg_off || !d_summary || !d_scratch) return -1;
-    if (datagrams > 0 && (!d_sched || !d_dg_len || !d_dg_class)) return -1;
-    if (groups > 0 && !d_first) return -1;
-    if (total_blocks > 0 && (!d_off || !d_len)) return -1;
-    if ((payload_bytes > 0 && !d_payload) || (recovery_bytes > 0 && !d_recovery) || (ring_bytes > 0 && !d_ring)) return -1;
-    if (n_pong > 0 && (!d_pong_at || !d_pong_val)) return -1;
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    hipStream_t s = pick(stream);
-    StreamState *st = stream_state(c, s);
-    if (!st) return -2;
-    sh::TxDatagramArgs a{};
-    a.sched = d_sched;
-    a.first = d_first;
-    a.payload = static_cast<const uint8_t *>(d_payload);
-    a.payload_bytes = payload_bytes;
-    a.off = d_off;
-    a.len = d_len;
-    a.recovery = static_cast<const uint8_t *>(d_recovery);
-    a.recovery_bytes = recovery_bytes;
-    a.group = d_group;
-    a.pong_at = d_pong_at;
-    a.pong_val = d_pong_val;
-    a.state_in = d_state_in;
-    a.state_out = d_state_out;
-    a.ring = static_cast<uint8_t *>(d_ring);
-    a.ring_bytes = ring_bytes;
-    a.dg_off = d_dg_off;
-    a.dg_len = d_dg_len;
-    a.dg_class = d_dg_class;
-    a.summary = d_summary;
-    a.errors = st->d_errors;
-    a.datagrams = datagrams;
-    a.groups = groups;
-    a.m = m;
-    a.B = block_bytes;
-    a.total = total_blocks;
-    a.n_pong = n_pong;
-    a.advance = advance;
-    a.align = align;
-    // under the stream's lock, like shorthair_frame_batch's count
-    std::lock_guard<std::mutex> g(st->mu);
-    SH_CHECK(sh::launch_tx_datagram(a, d_scratch, s));
-    return 0;
-}
-
-extern "C" long long shorthair_unframe_scratch_bytes(int groups, int emax) {
-    if (groups < 0 || emax < 1 || emax > 255) return -1;
-    const long long slots = static_cast<long long>(groups) * emax;
-    if (slots > 0x7fffffffll) return -1;
-    return sh::unframe_scratch_bytes(slots);
-}
-
-extern "C" int shorthair_unframe_batch(int block_bytes, int groups, int emax, long long group_stride_blocks,
-                                       const void *d_out, const int *d_out_count, void *d_payload,
-                                       long long payload_capacity, long long *d_off, int *d_len, void *d_scratch,
-                                       void *stream) {
-    if (block_bytes < 8 || block_bytes % 8 != 0 || groups < 0 || emax < 1 || emax > 255) return -1;
-    if (static_cast<long long>(groups) * emax > 0x7fffffffll) return -1;
-    if (group_stride_blocks < emax || payload_capacity < 0) return -1;
-    if (reinterpret_cast<uintptr_t>(d_out) % 8 != 0 || reinterpret_cast<uintptr_t>(d_off) % 8 != 0 ||
-        reinterpret_cast<uintptr_t>(d_len) % 4 != 0 || reinterpret_cast<uintptr_t>(d_scratch) % 8 != 0)
-        return -1;
-    if (groups > 0 && (!d_out || !d_off || !d_len || !d_scratch || (payload_capacity > 0 && !d_payload))) return -1;
-    if (groups == 0) return 0;
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    hipStream_t s = pick(stream);
-    StreamState *st = stream_state(c, s);
-    if (!st) return -2;
-    // under the stream's lock, like shorthair_frame_batch's count
-    std::lock_guard<std::mutex> g(st->mu);
-    SH_CHECK(sh::launch_unframe(block_bytes, groups, emax, group_stride_blocks, static_cast<const uint8_t *>(d_out),
-                                d_out_count, static_cast<uint8_t *>(d_payload), payload_capacity, d_off, d_len,
-                                d_scratch, st->d_errors, s));
-    return 0;
-}
-
 extern "C" int cauchy_256_batch_reserve(int k, int m, int block_bytes, int groups) {
     return cauchy_256_batch_reserve_stream(k, m, block_bytes, groups, nullptr);
 }
@@ -1354,21 +1017,16 @@ extern "C" int cauchy_256_batch_reserve_stream(int k, int m, int block_bytes, in
 }
 
 extern "C" int cauchy_256_batch_errors(void *stream) {
-    Context &c = ctx();
-    DeviceScope ds(c);
-    if (ds.rc) return ds.rc;
-    hipStream_t s = pick(stream);
-    StreamState *st = stream_state(c, s);
-    if (!st) return -2;
     // Read and clear in stream order, under the stream's lock: a decode enqueued on this stream
     // (by any thread) lands either before the read or after the clear, never in between.
-    std::lock_guard<std::mutex> g(st->mu);
+    sh::StreamCall call(stream);
+    if (call.rc) return call.rc;
     int *n = nullptr;
     SH_CHECK(hipHostMalloc(reinterpret_cast<void **>(&n), sizeof(int), hipHostMallocDefault));
     *n = 0;
-    hipError_t e = hipMemcpyAsync(n, st->d_errors, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemsetAsync(st->d_errors, 0, sizeof(int), s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    hipError_t e = hipMemcpyAsync(n, call.errors, sizeof(int), hipMemcpyDeviceToHost, call.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(call.errors, 0, sizeof(int), call.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(call.stream);
     const int r = *n;
     (void)hipHostFree(n);
     if (e != hipSuccess) {

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bytes.hpp"
 #include "frame.hpp"
 
 namespace sh {
@@ -19,29 +20,6 @@ namespace {
 constexpr int FRAME_THREADS = 256;
 constexpr int FRAME_WORDS = 2 * FRAME_THREADS;  // output words per workgroup
 constexpr int FRAME_MUL_NW = 4096;              // largest words-per-block divided by multiplication
-
-struct FrameArgs {
-    const uint8_t *payload;
-    long long payload_bytes;
-    const long long *off;
-    const int *len;
-    const uint8_t *raw;  // may be null
-    uint8_t *blocks;
-    int *errors;
-    long long total_words;  // total_blocks * nw
-    int B, nw;              // nw = B / 8
-    int head;               // 1: blocks is 8- but not 16-aligned, pairs start at word -1
-    uint32_t mul;           // floor(2^32 / nw) + 1 for 2 <= nw <= FRAME_MUL_NW (x / nw = umulhi(x, mul),
-                            // exact for x < 2^13), else 0
-};
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint64_t ld64(const uint8_t *p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);  // unaligned global_load_dwordx2
-    return v;
-}
 
 // What one output word takes from the payload buffer: n bytes (0..8) starting at byte `at`, placed
 // at byte `shl / 8` of the word, over the length prefix in word 0 of a framed block. A malformed block
@@ -150,22 +128,11 @@ __global__ __launch_bounds__(FRAME_THREADS) void frame_blocks(FrameArgs a) {
 
 }  // namespace
 
-hipError_t launch_frame(int B, int total_blocks, const uint8_t *payload, long long payload_bytes,
-                        const long long *off, const int *len, const uint8_t *raw, uint8_t *blocks, int *errors,
-                        hipStream_t stream) {
-    if (total_blocks <= 0) return hipSuccess;
-    FrameArgs a{};
-    a.payload = payload;
-    a.payload_bytes = payload_bytes;
-    a.off = off;
-    a.len = len;
-    a.raw = raw;
-    a.blocks = blocks;
-    a.errors = errors;
-    a.B = B;
-    a.nw = B / 8;
-    a.total_words = static_cast<long long>(total_blocks) * a.nw;
-    a.head = (reinterpret_cast<uintptr_t>(blocks) & 8) ? 1 : 0;
+hipError_t launch_frame(FrameArgs a, hipStream_t stream) {
+    if (a.total_blocks <= 0) return hipSuccess;
+    a.nw = a.B / 8;
+    a.total_words = static_cast<long long>(a.total_blocks) * a.nw;
+    a.head = (reinterpret_cast<uintptr_t>(a.blocks) & 8) ? 1 : 0;
     a.mul = (a.nw >= 2 && a.nw <= FRAME_MUL_NW) ? static_cast<uint32_t>((1ull << 32) / a.nw) + 1 : 0;
     const long long wgs = (a.total_words + a.head + FRAME_WORDS - 1) / FRAME_WORDS;
     if (wgs > 0x7fffffffll) return hipErrorInvalidValue;

@@ -40,6 +40,7 @@
 
 #include "../../include/shorthair_rx.h"
 #include "block_scan.hpp"
+#include "bytes.hpp"
 #include "rx_group.hpp"
 
 namespace sh {
@@ -63,8 +64,6 @@ static_assert(RXG_MAX % 64 == 0, "whole waves");
 constexpr int K_DATA = 0, K_OOB = 1, K_PONG = 2, K_SHORT = 3, K_WINDOW = 4, K_BAD = 7;
 constexpr int PONG = 16;
 
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1; }
-
 __device__ __forceinline__ int s7(int x) { return ((x & 127) ^ 64) - 64; }
 
 struct Agg {
@@ -82,30 +81,11 @@ __device__ __forceinline__ Agg combine(Agg a, Agg b) {
 __device__ __forceinline__ int apply(int u, Agg a) {
     return a.fp < 0 ? u : add_wrap(add_wrap(u, s7(a.fp - (u & 127))), a.sum);
 }
-__device__ __forceinline__ Agg shfl_up(Agg x, int d) { return Agg{__shfl_up(x.fp, d), __shfl_up(x.sum, d)}; }
-
-// Inclusive scan of the workgroup's Aggs in lane order; also the exclusive one and the total. wagg:
-// RXG_WAVES entries of LDS, free to rewrite after the next __syncthreads().
-__device__ __forceinline__ Agg wg_scan(Agg v, Agg *wagg, Agg &excl, Agg &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    Agg x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const Agg y = shfl_up(x, d);
-        if (lane >= d) x = combine(y, x);
-    }
-    Agg prev = shfl_up(x, 1);
-    if (lane == 0) prev = Agg{-1, 0};
-    if (lane == 63) wagg[wave] = x;
-    __syncthreads();
-    Agg pre{-1, 0};
-    total = Agg{-1, 0};
-    for (int w = 0; w < RXG_WAVES; ++w) {
-        if (w < wave) pre = combine(pre, wagg[w]);
-        total = combine(total, wagg[w]);
-    }
-    excl = combine(pre, prev);
-    return combine(pre, x);
-}
+// block_scan and scan_passes over Aggs, in datagram order.
+constexpr Agg AGG_NONE{-1, 0};
+struct AggCombine {
+    __device__ __forceinline__ Agg operator()(Agg a, Agg b) const { return combine(a, b); }
+};
 
 // Steps 1 to 3 for datagram i.
 __device__ __forceinline__ int classify(const RxGroupArgs &a, long long i) {
@@ -144,8 +124,7 @@ __global__ __launch_bounds__(RXG_THREADS) void rxg_classify(RxGroupArgs a) {
         code = classify(a, i);
         a.code[i] = code;
     }
-    Agg excl, total;
-    wg_scan(code_agg(code), wagg, excl, total);
+    const Agg total = block_scan<RXG_THREADS>(code_agg(code), wagg, AGG_NONE, AggCombine{}).total;
     if (threadIdx.x == 0) {
         a.tile_fp[blockIdx.x] = total.fp;
         a.tile_sum[blockIdx.x] = total.sum;
@@ -154,30 +133,14 @@ __global__ __launch_bounds__(RXG_THREADS) void rxg_classify(RxGroupArgs a) {
 
 __global__ __launch_bounds__(RXG_THREADS) void rxg_scan_tiles(RxGroupArgs a) {
     __shared__ Agg wagg[RXG_WAVES];
-    int u = a.state_in[0];
+    const int u = a.state_in[0];
     __syncthreads();  // every lane has read the state before lane 0 writes d_state_out, which may alias it
     if (threadIdx.x == 0) a.hdr[0] = u;
-    for (int base = 0; base < a.tiles; base += RXG_TILE_PASS) {
-        const int t0 = base + threadIdx.x * RXG_TILES_PER_LANE;
-        Agg ag[RXG_TILES_PER_LANE], mine{-1, 0};
-#pragma unroll
-        for (int j = 0; j < RXG_TILES_PER_LANE; ++j) {
-            ag[j] = t0 + j < a.tiles ? Agg{a.tile_fp[t0 + j], a.tile_sum[t0 + j]} : Agg{-1, 0};
-            mine = combine(mine, ag[j]);
-        }
-        Agg excl, total;
-        wg_scan(mine, wagg, excl, total);
-        int v = apply(u, excl);
-#pragma unroll
-        for (int j = 0; j < RXG_TILES_PER_LANE; ++j)
-            if (t0 + j < a.tiles) {
-                a.tile_u[t0 + j] = v;
-                v = apply(v, ag[j]);
-            }
-        u = apply(u, total);
-        __syncthreads();  // wagg is rewritten by the next pass
-    }
-    if (threadIdx.x == 0) a.state_out[0] = u;
+    // the tiles in front of tile t compose into one Agg: applied to u, it gives the group number in front of t
+    const Agg all = scan_passes<RXG_THREADS, RXG_TILES_PER_LANE>(
+        a.tiles, wagg, [&](long long t) { return Agg{a.tile_fp[t], a.tile_sum[t]}; },
+        [&](long long t, Agg in_front, Agg) { a.tile_u[t] = apply(u, in_front); }, AGG_NONE, AggCombine{});
+    if (threadIdx.x == 0) a.state_out[0] = apply(u, all);
 }
 
 __global__ __launch_bounds__(RXG_THREADS) void rxg_down(RxGroupArgs a) {
@@ -189,8 +152,7 @@ __global__ __launch_bounds__(RXG_THREADS) void rxg_down(RxGroupArgs a) {
     const bool have = i < a.datagrams;
     const int code = have ? a.code[i] : K_BAD;
     const bool data = (code & 15) == K_DATA;
-    Agg excl, total;
-    const Agg incl = wg_scan(code_agg(code), wagg, excl, total);
+    const Agg incl = block_scan<RXG_THREADS>(code_agg(code), wagg, AGG_NONE, AggCombine{}).incl;
     // steps 4 and 5
     const int u = apply(a.tile_u[t], incl);
     const long long slot64 = static_cast<long long>(static_cast<int>(static_cast<unsigned>(u) - static_cast<unsigned>(a.hdr[0]))) + a.back;
@@ -244,55 +206,27 @@ __global__ __launch_bounds__(RXG_THREADS) void rxg_scan_slots(RxGroupArgs a) {
     if (threadIdx.x < 8) s_sum[threadIdx.x] = threadIdx.x == 2 ? a.groups : 0;
     __syncthreads();
     // the tiles: where each one's datagrams start in d_other, and the four class counts
-    int carry = 0, st[4] = {0, 0, 0, 0};
-    for (int base = 0; base < a.tiles; base += RXG_TILE_PASS) {
-        const int t0 = base + threadIdx.x * RXG_TILES_PER_LANE;
-        int nb[RXG_TILES_PER_LANE], sum = 0;
-#pragma unroll
-        for (int j = 0; j < RXG_TILES_PER_LANE; ++j) {
-            nb[j] = t0 + j < a.tiles ? a.tile_nb[t0 + j] : 0;
-            sum += nb[j];
-            if (t0 + j < a.tiles)
-                for (int q = 0; q < 4; ++q) st[q] += a.tile_stat[4 * static_cast<long long>(t0 + j) + q];
-        }
-        int tot;
-        int at = carry + block_scan<RXG_THREADS>(sum, wsum, tot) - sum;
-#pragma unroll
-        for (int j = 0; j < RXG_TILES_PER_LANE; ++j)
-            if (t0 + j < a.tiles) {
-                a.tile_nb[t0 + j] = at;
-                at += nb[j];
-            }
-        carry += tot;
-        __syncthreads();  // wsum is rewritten by the next pass
-    }
+    int st[4] = {0, 0, 0, 0};
+    scan_passes<RXG_THREADS, RXG_TILES_PER_LANE>(
+        a.tiles, wsum,
+        [&](long long t) {
+            for (int q = 0; q < 4; ++q) st[q] += a.tile_stat[4 * t + q];
+            return a.tile_nb[t];
+        },
+        [&](long long t, int in_front, int) { a.tile_nb[t] = in_front; });
     for (int q = 0; q < 4; ++q)
         if (st[q]) atomicAdd(&s_sum[4 + q], st[q]);
     // the slots: d_pkt_first and the used range
-    int records = 0, lo = a.groups, hi = 0;
-    for (long long base = 0; base < a.groups; base += RXG_SLOT_PASS) {
-        const long long s0 = base + threadIdx.x * RXG_SLOT_TILE;  // 64-bit: groups near INT_MAX
-        int c[RXG_SLOT_TILE], sum = 0;
-#pragma unroll
-        for (int j = 0; j < RXG_SLOT_TILE; ++j) {
-            c[j] = s0 + j < a.groups ? a.cnt[s0 + j] : 0;
-            sum += c[j];
-        }
-        int tot;
-        int at = records + block_scan<RXG_THREADS>(sum, wsum, tot) - sum;
-#pragma unroll
-        for (int j = 0; j < RXG_SLOT_TILE; ++j)
-            if (s0 + j < a.groups) {
-                at += c[j];
-                a.pkt_first[s0 + j + 1] = at;
-                if (c[j]) {
-                    lo = min(lo, static_cast<int>(s0 + j));
-                    hi = static_cast<int>(s0 + j) + 1;
-                }
+    int lo = a.groups, hi = 0;
+    const int records = scan_passes<RXG_THREADS, RXG_SLOT_TILE>(
+        a.groups, wsum, [&](long long s) { return a.cnt[s]; },
+        [&](long long s, int in_front, int c) {
+            a.pkt_first[s + 1] = in_front + c;
+            if (c) {
+                lo = min(lo, static_cast<int>(s));
+                hi = static_cast<int>(s) + 1;
             }
-        records += tot;
-        __syncthreads();
-    }
+        });
     if (hi) {
         atomicMin(&s_sum[2], lo);
         atomicMax(&s_sum[3], hi);
@@ -315,8 +249,7 @@ __global__ __launch_bounds__(RXG_THREADS) void rxg_scatter(RxGroupArgs a) {
     const bool have = i < a.datagrams;
     const int slot = have ? a.dg_slot[i] : 0;
     const int nb = have && slot < 0;
-    int tot;
-    const int rank = block_scan<RXG_THREADS>(nb, wsum, tot) - nb;
+    const int rank = block_scan<RXG_THREADS>(nb, wsum).excl;
     if (!have) return;
     const int records = a.summary[0];
     // the tails first: [records, datagrams) of the record lists, [datagrams - records, datagrams) of d_other

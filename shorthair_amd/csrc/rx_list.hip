@@ -24,6 +24,7 @@
 
 #include "../../include/shorthair_rx.h"
 #include "block_scan.hpp"
+#include "bytes.hpp"
 #include "rx_list.hpp"
 
 namespace sh {
@@ -40,8 +41,6 @@ static_assert(RX_INFO == 8, "lanes 0..7 write d_info[g]");
 
 // header word in LDS: id | c << 8 | class << 16
 constexpr uint32_t CLS_ORIG = 1, CLS_REC = 2;
-
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1; }
 
 // Step 0: the records of group g, [f0, f0 + n); ok = false (and n = 0) for a malformed span.
 struct Span {
@@ -168,68 +167,57 @@ __global__ __launch_bounds__(RX_THREADS) void rx_classify(RxListArgs a) {
     if (lane == 0) a.code[g] = ((status == 1 ? k : 0) << 8) | (status + 1);
 }
 
+// What rx_scan scans: a group that step 8 lists is {k, 1}, any other {0, 0}. The blocks in front of a
+// group can pass the capacity (step 9), the slots cannot pass INT_MAX.
+struct __attribute__((packed, aligned(4))) Listed {
+    long long blocks;
+    int slots;
+};
+struct ListedAdd {
+    __device__ __forceinline__ Listed operator()(Listed x, Listed y) const {
+        return Listed{x.blocks + y.blocks, x.slots + y.slots};
+    }
+};
+
 __global__ __launch_bounds__(RX_THREADS) void rx_scan(RxListArgs a) {
-    __shared__ long long wsum[RX_WAVES];
-    __shared__ int wcnt[RX_WAVES];
+    __shared__ Listed wsum[RX_WAVES];
     __shared__ int s_sum[8];  // d_summary
     if (threadIdx.x < 8) s_sum[threadIdx.x] = 0;
     __syncthreads();
-    long long carry_blocks = 0;  // blocks of the groups that step 8 listed (it can pass the capacity: step 9)
-    int carry_slots = 0;
     int listed = 0, end = 0, skipped = 0, k1 = 0, other = 0, malformed = 0;
-    for (long long base = 0; base < a.groups; base += RX_PASS) {
-        const long long g0 = base + threadIdx.x * RX_TILE;  // 64-bit: groups near INT_MAX
-        int code[RX_TILE];
-#pragma unroll
-        for (int i = 0; i < RX_TILE; ++i) code[i] = g0 + i < a.groups ? a.code[g0 + i] : 1;  // (past the end: skipped, not counted)
-        long long sum = 0;
-        int cnt = 0;
-#pragma unroll
-        for (int i = 0; i < RX_TILE; ++i)
-            if ((code[i] & 255) == 2) {
-                sum += code[i] >> 8;
-                ++cnt;
-            }
-        long long tot_blocks;
-        int tot_slots;
-        long long b = carry_blocks + block_scan<RX_THREADS>(sum, wsum, tot_blocks) - sum;
-        int slot = carry_slots + block_scan<RX_THREADS>(cnt, wcnt, tot_slots) - cnt;
-#pragma unroll
-        for (int i = 0; i < RX_TILE; ++i) {
-            const long long g = g0 + i;
-            int status = (code[i] & 255) - 1;
-            const int k = code[i] >> 8;
+    scan_passes<RX_THREADS, RX_TILE>(
+        a.groups, wsum,
+        [&](long long g) {
+            const int code = a.code[g], status = (code & 255) - 1;
+            skipped += status == 0;
+            k1 += status == 2;
+            other += status == 3;
+            malformed += status < 0;
+            return status == 1 ? Listed{code >> 8, 1} : Listed{0, 0};
+        },
+        [&](long long g, Listed in_front, Listed item) {
             int at = -1;
-            if (status == 1) {  // (never past the end: those are "skipped")
+            if (item.slots) {
+                const long long b = in_front.blocks;
+                const int slot = in_front.slots, k = static_cast<int>(item.blocks);
                 if (b + k <= a.capacity) {
                     a.info[g * RX_INFO + 6] = slot;
                     a.slot_group[slot] = static_cast<int>(g);
                     a.first[slot + 1] = static_cast<int>(b) + k;
                     at = static_cast<int>(b);
                     end = at + k;
-                    ++slot;
                     ++listed;
                 } else {  // step 9; every listed group after this one fails it too
-                    status = -1;
+                    ++malformed;
                     int *info = a.info + g * RX_INFO;
                     info[0] = -1;
                     for (int j = 1; j < 6; ++j) info[j] = 0;
                     info[6] = info[7] = -1;
                 }
-                b += k;
             }
-            if (g < a.groups) {
-                a.base[g] = at;
-                skipped += status == 0;
-                k1 += status == 2;
-                other += status == 3;
-                malformed += status < 0;
-            }
-        }
-        carry_blocks += tot_blocks;
-        carry_slots += tot_slots;
-        __syncthreads();  // wsum and wcnt are rewritten by the next pass
-    }
+            a.base[g] = at;
+        },
+        Listed{0, 0}, ListedAdd{});
     if (listed) {
         atomicAdd(&s_sum[0], listed);
         atomicMax(&s_sum[1], end);

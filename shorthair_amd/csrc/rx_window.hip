@@ -172,6 +172,7 @@ __global__ __launch_bounds__(RXW_THREADS) void rxw_scan(RxWindowArgs a) {
     unsigned long long mine[RXW_STATS + 2] = {0, 0, 0, 0, 0, 0, 0};
     for (long long q = threadIdx.x; q < static_cast<long long>(a.wgs) * RXW_STATS; q += RXW_THREADS)
         mine[q % RXW_STATS] += static_cast<unsigned long long>(a.wg_stat[q]);
+    // (not scan_passes: the cut is a workgroup-wide maximum between two walks over the lane's slots)
     long long carry_r = 0, carry_b = 0;
     for (long long base = 0; base < a.groups; base += RXW_SCAN_PASS) {
         const long long s0 = base + threadIdx.x * RXW_SCAN_TILE;
@@ -186,9 +187,9 @@ __global__ __launch_bounds__(RXW_THREADS) void rxw_scan(RxWindowArgs a) {
             sum_r += static_cast<long long>(cc[j]) + cn[j];
             sum_b += b[j];
         }
-        long long tot_r, tot_b;
-        const long long r0 = carry_r + block_scan<RXW_THREADS>(sum_r, wsum_r, tot_r) - sum_r;
-        const long long b0 = carry_b + block_scan<RXW_THREADS>(sum_b, wsum_b, tot_b) - sum_b;
+        const Scanned<long long> sc_r = block_scan<RXW_THREADS>(sum_r, wsum_r);
+        const Scanned<long long> sc_b = block_scan<RXW_THREADS>(sum_b, wsum_b);
+        const long long r0 = carry_r + sc_r.excl, b0 = carry_b + sc_b.excl;
         // the last slot of this lane that still fits: both sums are monotone, so the largest is the cut
         long long at_r = r0, at_b = b0, fit_r = -1, fit_b = 0;
 #pragma unroll
@@ -223,8 +224,8 @@ __global__ __launch_bounds__(RXW_THREADS) void rxw_scan(RxWindowArgs a) {
                 if (!over) mine[RXW_STATS + 1] += static_cast<unsigned>(cc[j]);
             }
         }
-        carry_r += tot_r;
-        carry_b += tot_b;
+        carry_r += sc_r.total;
+        carry_b += sc_b.total;
         __syncthreads();  // wsum_r and wsum_b are rewritten by the next pass
     }
 #pragma unroll
@@ -264,10 +265,10 @@ __global__ __launch_bounds__(RXW_THREADS) void rxw_carry(RxWindowArgs a) {
 }
 
 __global__ __launch_bounds__(RXW_THREADS) void rxw_place(RxWindowArgs a) {
-    const long long t = static_cast<long long>(blockIdx.x) * RXW_THREADS + threadIdx.x;
-    const long long r = t >> a.lshift;
+    const LaneSplit ls = lane_split(static_cast<long long>(blockIdx.x) * RXW_THREADS + threadIdx.x, a.lshift);
+    const long long r = ls.item;
     if (r >= a.n_cap) return;
-    const int step = 1 << a.lshift, sub = static_cast<int>(t) & (step - 1);
+    const int sub = ls.sub;
     if (r >= a.n_first[a.groups]) {  // the tails
         if (sub == 0) {
             a.n_off[r] = 0;
@@ -296,7 +297,7 @@ __global__ __launch_bounds__(RXW_THREADS) void rxw_place(RxWindowArgs a) {
     }
     if (a.copy) {  // a carried record: rxw_carry wrote its place
         const TxCopy c = rxw_copy_plan(a.ring, a.ring_bytes, a.p_off[static_cast<long long>(a.src_c[s]) + j], a.n_len[r]);
-        txd_copy_lane(c, a.ring + a.n_off[r], sub, step);
+        txd_copy_lane(c, a.ring + a.n_off[r], sub, ls.step);
     }
 }
 

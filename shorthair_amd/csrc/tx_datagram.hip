@@ -136,8 +136,7 @@ __global__ __launch_bounds__(TXD_THREADS) void txd_lengths(TxDatagramArgs a) {
     }
     const int L = hlen + blen;                        // <= SHORTHAIR_TX_MAX_DATAGRAM_BYTES
     const int v = (L + a.align - 1) & ~(a.align - 1);  // <= 69,632: a tile sums to < 2^25
-    int total;
-    const int incl = block_scan<TXD_THREADS>(v, wsum, total);  // (its barrier also publishes stat[] = 0)
+    const Scanned<int> sc = block_scan<TXD_THREADS>(v, wsum);  // (its barrier also publishes stat[] = 0)
     if (in) {
         a.dg_len[i] = L;
         a.dg_class[i] = cls;
@@ -146,10 +145,10 @@ __global__ __launch_bounds__(TXD_THREADS) void txd_lengths(TxDatagramArgs a) {
         d.h1 = h1;
         d.src = src;
         d.meta = blen | (hlen << TXD_HLEN_SHIFT) | rec;
-        d.local = incl - v;
+        d.local = sc.excl;
         a.desc[i] = d;
     }
-    if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
+    if (threadIdx.x == 0) a.sums[blockIdx.x] = sc.total;
     // class counts: ballots, one LDS atomic per wave and class
     const bool flag[TXD_STATS] = {in && L > 0,      in && (cls == 0 || cls == 8), in && (cls == 1 || cls == 2),
                                   in && (cls & ~8) == 3 && cls >= 0, in && cls >= 8,              in && cls == -1};
@@ -167,32 +166,15 @@ __global__ __launch_bounds__(TXD_THREADS) void txd_scan(TxDatagramArgs a) {
     __shared__ int stat[TXD_STATS];
     if (threadIdx.x < TXD_STATS) stat[threadIdx.x] = 0;
     const int s0 = a.state_in[0], s1 = a.state_in[1];
-    long long carry = 0;
     int mine[TXD_STATS] = {0, 0, 0, 0, 0, 0};
-    for (int base = 0; base < a.tiles; base += TXD_TILE_PASS) {
-        // a lane sums TXD_PER_LANE consecutive tiles, the workgroup scans the lanes' sums
-        const int t0 = base + static_cast<int>(threadIdx.x) * TXD_PER_LANE;
-        long long v[TXD_PER_LANE], sum = 0;
+    const long long carry = scan_passes<TXD_THREADS, TXD_PER_LANE>(
+        a.tiles, wsum,
+        [&](long long t) {
 #pragma unroll
-        for (int j = 0; j < TXD_PER_LANE; ++j) {
-            const int t = t0 + j;
-            v[j] = t < a.tiles ? a.sums[t] : 0;
-            sum += v[j];
-            if (t < a.tiles) {
-#pragma unroll
-                for (int c = 0; c < TXD_STATS; ++c) mine[c] += a.tile_stat[t * TXD_STATS + c];
-            }
-        }
-        long long total;
-        long long at = carry + block_scan<TXD_THREADS>(sum, wsum, total) - sum;
-#pragma unroll
-        for (int j = 0; j < TXD_PER_LANE; ++j) {
-            if (t0 + j < a.tiles) a.sums[t0 + j] = at;
-            at += v[j];
-        }
-        carry += total;
-        __syncthreads();  // wsum is rewritten by the next pass
-    }
+            for (int c = 0; c < TXD_STATS; ++c) mine[c] += a.tile_stat[t * TXD_STATS + c];
+            return a.sums[t];
+        },
+        [&](long long t, long long base, long long) { a.sums[t] = base; });
     __syncthreads();  // stat[] = 0 is visible, and every lane has read the state (out may alias in)
 #pragma unroll
     for (int c = 0; c < TXD_STATS; ++c)
@@ -211,18 +193,16 @@ __global__ __launch_bounds__(TXD_THREADS) void txd_scan(TxDatagramArgs a) {
 }
 
 __global__ __launch_bounds__(TXD_THREADS) void txd_copy(TxDatagramArgs a) {
-    const long long t = static_cast<long long>(blockIdx.x) * TXD_THREADS + threadIdx.x;
-    const long long dl = t >> a.lshift;
-    const bool ok = dl < a.datagrams;
-    const uint32_t i = ok ? static_cast<uint32_t>(dl) : 0;  // (a lane past the last datagram reads datagram 0's descriptor and drops it)
-    const int step = 1 << a.lshift, sub = static_cast<int>(t) & (step - 1);
+    const LaneSplit ls = lane_split(static_cast<long long>(blockIdx.x) * TXD_THREADS + threadIdx.x, a.lshift);
+    const bool ok = ls.item < a.datagrams;
+    const uint32_t i = ok ? static_cast<uint32_t>(ls.item) : 0;  // (a lane past the last datagram reads datagram 0's descriptor and drops it)
     const TxDesc d = a.desc[i];
     const long long off = a.sums[i / TXD_TILE] + d.local;
     TxCopy c = txd_plan(d, a.payload, a.payload_bytes, a.recovery);
     const bool over = c.L > 0 && off > a.ring_bytes - c.L;  // not written at all
-    const bool first = ok && sub == 0;
+    const bool first = ok && ls.sub == 0;
     if (first) a.dg_off[i] = off;
-    if (ok && !over) txd_copy_lane(c, a.ring + off, sub, step);
+    if (ok && !over) txd_copy_lane(c, a.ring + off, ls.sub, ls.step);
     // datagrams that do not fit: the first lane takes the class back out of the summary
     const unsigned long long b = __ballot(first && over);
     if (b) {  // wave-uniform
@@ -261,9 +241,7 @@ hipError_t launch_tx_datagram(TxDatagramArgs a, void *scratch, hipStream_t strea
     a.desc = static_cast<TxDesc *>(scratch);
     a.sums = reinterpret_cast<long long *>(a.desc + a.datagrams);
     a.tile_stat = reinterpret_cast<int *>(a.sums + a.tiles + 1);
-    a.lshift = 0;
-    const int hint = a.B > 0 ? a.B + 14 + 15 : 512;  // (15: a piece more where the destination is unaligned)
-    while (a.lshift < 5 && (16 << a.lshift) < hint) ++a.lshift;
+    a.lshift = lshift_for(a.B > 0 ? a.B + 14 + 15 : 512);  // (15: a piece more where the destination is unaligned)
     if (a.tiles > 0) hipLaunchKernelGGL(txd_lengths, dim3(static_cast<unsigned>(a.tiles)), dim3(TXD_THREADS), 0, stream, a);
     hipLaunchKernelGGL(txd_scan, dim3(1), dim3(TXD_THREADS), 0, stream, a);
     if (a.tiles > 0) {

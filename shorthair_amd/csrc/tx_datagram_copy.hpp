@@ -14,9 +14,7 @@
 
 #include <stdint.h>
 
-#ifndef SH_TXD_FN
-#define SH_TXD_FN __device__ __forceinline__
-#endif
+#include "bytes.hpp"
 
 namespace sh {
 
@@ -30,8 +28,6 @@ struct TxDesc {
 constexpr int TXD_REC = 1 << 24;
 constexpr int TXD_HLEN_SHIFT = 20;
 constexpr int TXD_BLEN_MASK = (1 << TXD_HLEN_SHIFT) - 1;
-
-typedef uint64_t txd_u64x2 __attribute__((ext_vector_type(2)));
 
 SH_TXD_FN int txd_min(int a, int b) { return a < b ? a : b; }
 SH_TXD_FN int txd_max(int a, int b) { return a > b ? a : b; }
@@ -110,41 +106,20 @@ SH_TXD_FN uint64_t txd_finish(const TxCopy &c, const TxWord &w, uint64_t x, int 
     return ((x & mask) << w.shl) | txd_header_word(c, d0);
 }
 
-// n (0..8) low bytes of v to dst, at any alignment: one 8-byte store, or 4 + 2 + 1.
-SH_TXD_FN void txd_store_bytes(uint8_t *dst, uint64_t v, int n) {
-    if (n >= 8) {
-        __builtin_memcpy(dst, &v, 8);
-        return;
-    }
-    if (n & 4) {
-        const uint32_t t = static_cast<uint32_t>(v);
-        __builtin_memcpy(dst, &t, 4);
-        dst += 4;
-        v >>= 32;
-    }
-    if (n & 2) {
-        const uint16_t t = static_cast<uint16_t>(v);
-        __builtin_memcpy(dst, &t, 2);
-        dst += 2;
-        v >>= 16;
-    }
-    if (n & 1) *dst = static_cast<uint8_t>(v);
-}
-
 // The word over datagram bytes [d0, d0 + 8): those inside [0, L) go to dst + their index.
 SH_TXD_FN void txd_emit_word(uint8_t *dst, const TxCopy &c, int d0, uint64_t v) {
     const int lo = txd_max(d0, 0);
     const int n = txd_min(d0 + 8, c.L) - lo;
-    if (n > 0) txd_store_bytes(dst + lo, v >> (8 * (lo - d0)), n);
+    if (n > 0) store_bytes(dst + lo, v >> (8 * (lo - d0)), n);
 }
 
 // Piece p: d0 = 16p - a. Whole: one aligned 16-byte store.
 SH_TXD_FN void txd_emit_piece(uint8_t *dst, const TxCopy &c, int d0, uint64_t v0, uint64_t v1) {
     if (d0 >= 0 && d0 + 16 <= c.L) {
-        txd_u64x2 o;
+        u64x2 o;
         o.x = v0;
         o.y = v1;
-        *reinterpret_cast<txd_u64x2 *>(dst + d0) = o;  // global_store_dwordx4
+        *reinterpret_cast<u64x2 *>(dst + d0) = o;  // global_store_dwordx4
         return;
     }
     txd_emit_word(dst, c, d0, v0);

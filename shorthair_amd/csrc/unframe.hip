@@ -19,6 +19,7 @@
 
 #include "../../include/shorthair_unframe.h"
 #include "block_scan.hpp"
+#include "bytes.hpp"
 #include "unframe.hpp"
 
 namespace sh {
@@ -28,23 +29,6 @@ constexpr int UNFRAME_THREADS = 256;
 constexpr int UNFRAME_TILE = SHORTHAIR_UNFRAME_TILE_SLOTS;  // slots per workgroup of unframe_lengths
 constexpr int UNFRAME_SCAN_PASS = SHORTHAIR_UNFRAME_SCAN_PASS;
 static_assert(UNFRAME_TILE == UNFRAME_THREADS && UNFRAME_SCAN_PASS == UNFRAME_THREADS, "a lane per slot / per sum");
-
-struct UnframeArgs {
-    const uint8_t *out;
-    const int *count;  // may be null
-    uint8_t *payload;
-    long long capacity;
-    long long *off;
-    int *len;
-    long long *sums;  // [tiles + 1]
-    int *local;       // [slots]
-    int *errors;
-    long long stride_blocks;
-    int slots, tiles, emax, B;
-    int lshift;  // unframe_copy: 1 << lshift lanes per slot
-};
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 // The block of slot s, in blocks from `out`.
 __device__ __forceinline__ long long slot_block(const UnframeArgs &a, uint32_t s) {
@@ -72,10 +56,9 @@ __global__ __launch_bounds__(UNFRAME_THREADS) void unframe_lengths(UnframeArgs a
         a.len[s] = len;
     }
     const int v = max(len, 0);  // <= 65535: a tile sums to < 2^24
-    int total;
-    const int incl = block_scan<UNFRAME_THREADS>(v, wsum, total);
-    if (in) a.local[s] = incl - v;
-    if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
+    const Scanned<int> sc = block_scan<UNFRAME_THREADS>(v, wsum);
+    if (in) a.local[s] = sc.excl;
+    if (threadIdx.x == 0) a.sums[blockIdx.x] = sc.total;
     // as var_check (kernels.hip): a ballot, then one atomicAdd per wave
     const int n = __popcll(__ballot(report));
     if (n && (threadIdx.x & 63) == 0) atomicAdd(a.errors, n);
@@ -83,41 +66,13 @@ __global__ __launch_bounds__(UNFRAME_THREADS) void unframe_lengths(UnframeArgs a
 
 __global__ __launch_bounds__(UNFRAME_THREADS) void unframe_scan(UnframeArgs a) {
     __shared__ long long wsum[UNFRAME_THREADS / 64];
-    long long carry = 0;
-    for (int base = 0; base < a.tiles; base += UNFRAME_SCAN_PASS) {
-        const int t = base + static_cast<int>(threadIdx.x);
-        const long long v = t < a.tiles ? a.sums[t] : 0;
-        long long total;
-        const long long incl = block_scan<UNFRAME_THREADS>(v, wsum, total);
-        if (t < a.tiles) a.sums[t] = carry + incl - v;
-        carry += total;
-        __syncthreads();  // wsum is rewritten by the next pass
-    }
+    const long long total = scan_passes<UNFRAME_THREADS, UNFRAME_SCAN_PASS / UNFRAME_THREADS>(
+        a.tiles, wsum, [&](long long t) { return a.sums[t]; },
+        [&](long long t, long long base, long long) { a.sums[t] = base; });
     if (threadIdx.x == 0) {
-        a.sums[a.tiles] = carry;
-        a.off[a.slots] = carry;
+        a.sums[a.tiles] = total;
+        a.off[a.slots] = total;
     }
-}
-
-// n (0..8) low bytes of v to dst, at any alignment: one 8-byte store, or 4 + 2 + 1.
-__device__ __forceinline__ void store_bytes(uint8_t *dst, uint64_t v, int n) {
-    if (n >= 8) {
-        __builtin_memcpy(dst, &v, 8);  // unaligned global_store_dwordx2
-        return;
-    }
-    if (n & 4) {
-        const uint32_t t = static_cast<uint32_t>(v);
-        __builtin_memcpy(dst, &t, 4);
-        dst += 4;
-        v >>= 32;
-    }
-    if (n & 2) {
-        const uint16_t t = static_cast<uint16_t>(v);
-        __builtin_memcpy(dst, &t, 2);
-        dst += 2;
-        v >>= 16;
-    }
-    if (n & 1) *dst = static_cast<uint8_t>(v);
 }
 
 // Word w of a slot's block: its payload bytes -- block bytes [8w, 8w + 8) cut to [2, 2 + p) -- go to
@@ -150,11 +105,10 @@ __device__ __forceinline__ void emit_chunk(uint8_t *dst, int c, int p, u64x2 x) 
 }
 
 __global__ __launch_bounds__(UNFRAME_THREADS) void unframe_copy(UnframeArgs a) {
-    const long long t = static_cast<long long>(blockIdx.x) * UNFRAME_THREADS + threadIdx.x;
-    const long long sl = t >> a.lshift;
-    const bool ok = sl < a.slots;
-    const uint32_t s = ok ? static_cast<uint32_t>(sl) : 0;  // (a lane past the last slot reads slot 0's descriptor and drops it)
-    const int step = 1 << a.lshift, sub = static_cast<int>(t) & (step - 1);
+    const LaneSplit ls = lane_split(static_cast<long long>(blockIdx.x) * UNFRAME_THREADS + threadIdx.x, a.lshift);
+    const bool ok = ls.item < a.slots;
+    const uint32_t s = ok ? static_cast<uint32_t>(ls.item) : 0;  // (a lane past the last slot reads slot 0's descriptor and drops it)
+    const int step = ls.step, sub = ls.sub;
     const int p = a.len[s];
     const long long off = a.sums[s / UNFRAME_TILE] + a.local[s];
     if (ok && sub == 0) a.off[s] = off;
@@ -184,24 +138,11 @@ long long unframe_scratch_bytes(long long slots) {
     return 8 * (tiles + 1) + 4 * slots;
 }
 
-hipError_t launch_unframe(int B, int groups, int emax, long long stride_blocks, const uint8_t *out,
-                          const int *count, uint8_t *payload, long long capacity, long long *off, int *len,
-                          void *scratch, int *errors, hipStream_t stream) {
-    if (groups <= 0) return hipSuccess;
-    UnframeArgs a{};
-    a.out = out;
-    a.count = count;
-    a.payload = payload;
-    a.capacity = capacity;
-    a.off = off;
-    a.len = len;
-    a.errors = errors;
-    a.stride_blocks = stride_blocks;
-    a.slots = groups * emax;
+hipError_t launch_unframe(UnframeArgs a, void *scratch, hipStream_t stream) {
+    if (a.groups <= 0) return hipSuccess;
+    a.slots = a.groups * a.emax;
     a.tiles = (a.slots - 1) / UNFRAME_TILE + 1;
-    a.emax = emax;
-    a.B = B;
-    while (a.lshift < 5 && (16 << a.lshift) < B) ++a.lshift;
+    a.lshift = lshift_for(a.B);
     a.sums = static_cast<long long *>(scratch);
     a.local = reinterpret_cast<int *>(a.sums + a.tiles + 1);
     // slots <= INT_MAX, 32 lanes each at most: always within a grid

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bytes.hpp"
 #include "wire.hpp"
 
 namespace sh {
@@ -19,27 +20,6 @@ namespace {
 constexpr int WIRE_THREADS = 256;
 constexpr int WIRE_BYTES = 16 * WIRE_THREADS;  // output bytes per workgroup
 constexpr int WIRE_MUL_S = 32768;              // largest record size divided by multiplication
-
-struct WireArgs {
-    const uint8_t *rec;
-    uint8_t *wire;
-    const int *first;  // null: every group has k originals
-    long long run;     // groups * m * S: bytes written
-    long long src;     // groups * m * B: bytes of rec
-    int S, B, m, k, groups, total;
-    int head;        // wire & 15: the run starts `head` bytes into workgroup 0's first piece
-    uint32_t mul_s;  // floor(2^32 / S) + 1 for S <= WIRE_MUL_S (x / S = umulhi(x, mul_s), exact for
-                     // x < S + WIRE_BYTES as (S + WIRE_BYTES) * S < 2^32), else 0
-    uint32_t mul_m;  // floor(2^32 / m) + 1 for m >= 2 (exact for x < 2^32 / m; x < m + 375 here)
-};
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint64_t ld64(const uint8_t *p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);  // unaligned global_load_dwordx2
-    return v;
-}
 
 // The header of recovery block y of a group whose first[] entries are f0, f1 (unused when uniform), as
 // the low 3 bytes of a word; ok = false for a group malformed by var_group's rule (geometry.hpp).
@@ -154,28 +134,18 @@ __global__ __launch_bounds__(WIRE_THREADS) void wire_emit(WireArgs a) {
 
 }  // namespace
 
-hipError_t launch_wire_emit(int k, int m, int B, int groups, const int *first, int total_blocks,
-                            const uint8_t *recovery, uint8_t *wire, hipStream_t stream) {
-    if (groups <= 0) return hipSuccess;
-    WireArgs a{};
-    a.rec = recovery;
-    a.wire = wire;
-    a.first = first;
-    a.S = 3 + B;
-    a.B = B;
-    a.m = m;
-    a.k = k;
-    a.groups = groups;
-    a.total = total_blocks;
-    const long long records = static_cast<long long>(groups) * m;
+hipError_t launch_wire_emit(WireArgs a, hipStream_t stream) {
+    if (a.groups <= 0) return hipSuccess;
+    a.S = 3 + a.B;
+    const long long records = static_cast<long long>(a.groups) * a.m;
     a.run = records * a.S;
-    a.src = records * B;
-    a.head = static_cast<int>(reinterpret_cast<uintptr_t>(wire) & 15);
+    a.src = records * a.B;
+    a.head = static_cast<int>(reinterpret_cast<uintptr_t>(a.wire) & 15);
     a.mul_s = a.S <= WIRE_MUL_S ? static_cast<uint32_t>((1ull << 32) / a.S) + 1 : 0;
-    a.mul_m = m >= 2 ? static_cast<uint32_t>((1ull << 32) / m) + 1 : 0;
+    a.mul_m = a.m >= 2 ? static_cast<uint32_t>((1ull << 32) / a.m) + 1 : 0;
     const long long wgs = (a.run + a.head + WIRE_BYTES - 1) / WIRE_BYTES;
     if (wgs > 0x7fffffffll) return hipErrorInvalidValue;
-    if (first)
+    if (a.first)
         hipLaunchKernelGGL(wire_emit<true>, dim3(static_cast<unsigned>(wgs)), dim3(WIRE_THREADS), 0, stream, a);
     else
         hipLaunchKernelGGL(wire_emit<false>, dim3(static_cast<unsigned>(wgs)), dim3(WIRE_THREADS), 0, stream, a);
